@@ -14,12 +14,17 @@ per GPU, problems sharded (weak scaling), plus one RCCL all-gather of the
 packed sensitivities per step (§8(e)).  `--lam-eps 1e-9` gives the inactive
 rows tiny non-zero duals (interior-point-like: no exact elimination, N' = n+m).
 
-  python bench.py [--gpus N] [--steps K] [--warmup W]
+  python bench.py [--gpus N] [--steps K] [--warmup W] [--dump-outputs DIR] [--full]
   torchrun --nproc-per-node N bench.py --gpus N ...   (driver, N > 1)
 
-Prints ONE JSON line on rank 0 (the driver's contract), with `roofline`
-(dominant kernel, timed live with HIP events on the engine's stream) and
-`cpu_baseline` (the oracle restatement timed on the host's cores).
+Prints ONE JSON line on rank 0 (the driver's contract).  A plain run sets up,
+warms up, times the K steps and prints the line; `roofline` and `cpu_baseline`
+are null.  `--full` adds what takes runs of its own: `roofline` (the untimed
+per-phase pass, then the dominant kernel timed live with HIP events on the
+engine's stream) and `cpu_baseline` (the oracle restatement timed on the
+host's cores).  `--dump-outputs DIR` writes the arrays the last timed step
+returned as DIR/<name>.npy (float64); the inputs are seeded, so two builds
+can be compared output for output.
 """
 
 import argparse
@@ -79,6 +84,32 @@ def host_cores():
 
 def cpu_workers(args):
     return args.cpu_workers or host_cores()[0]
+
+
+def want_cpu_baseline(args, world, rank):
+    return args.full and not args.no_cpu_baseline and rank == 0 and world == 1
+
+
+DUMP_LIMIT_BYTES = 60 * 10 ** 6   # array payload; with the .npy headers the files stay below 64 MB
+
+
+def dump_outputs(path, arrays):
+    """--dump-outputs: `arrays` (name → device tensor or ndarray, what the last
+    timed step returned to its caller) as path/<name>.npy in float64.  Together
+    at most DUMP_LIMIT_BYTES: an array above its equal share of that is cut
+    down to a fixed seeded sample of its elements (sorted flat indices, the
+    same for every run of the same shape)."""
+    import numpy as np
+    os.makedirs(path, exist_ok=True)
+    share = DUMP_LIMIT_BYTES // max(len(arrays), 1)
+    for name, a in arrays.items():
+        if hasattr(a, "detach"):
+            a = a.detach().cpu().numpy()
+        a = np.ascontiguousarray(a, dtype=np.float64)
+        if a.nbytes > share:
+            idx = np.sort(np.random.default_rng(20250307).choice(a.size, share // 8, replace=False))
+            a = a.reshape(-1)[idx]
+        np.save(os.path.join(path, name + ".npy"), a)
 
 
 # --------------------------------------------------------------------------
@@ -151,7 +182,7 @@ def run_nlp(args, world, rank, local_rank):
     B = args.batch or cfg["batch"]
     n, c, P = cfg["n"], cfg["c"], cfg["P"]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu_baseline(args, world, rank):
         import multiprocessing as mp
         workers = cpu_workers(args)
         t0 = time.perf_counter()
@@ -185,22 +216,22 @@ def run_nlp(args, world, rank, local_rank):
     def step():
         eng.factor()
         if args.nlp_separate:   # the reference's two calls: forward_differentiate!, reverse_differentiate!
-            eng.forward(dp_t)
-            eng.reverse(dx_t, dd_t)
-        else:
-            eng.forward_reverse(dp_t, dx_t, dd_t)   # forward + reverse, one pass over the factors for both
+            return (*eng.forward(dp_t), eng.reverse(dx_t, dd_t))
+        return eng.forward_reverse(dp_t, dx_t, dd_t)   # forward + reverse, one pass over the factors for both
 
     for _ in range(args.warmup):
         step()
-    breakdown, name = _phase_breakdown(eng, step, 3)
-    eng.phase_times()
-    eng.set_profiling(True, phases=[name])
+    if args.full:
+        breakdown, name = _phase_breakdown(eng, step, 3)
+        eng.phase_times()
+        eng.set_profiling(True, phases=[name])
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -214,7 +245,10 @@ def run_nlp(args, world, rank, local_rank):
     corr = eng.corrections()
     kinds = eng.lu_kind()
     sizes = eng.system_size().astype(np.float64)   # R (n + c) on the reduced route, M's rows on the full one
-    if rank == 0:
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, dict(zip(("forward_dx", "forward_ddual", "reverse_dp"), last)))
+    roof = None
+    if rank == 0 and args.full:
         ms_tot, cnt = phases[name]   # live, over the timed region
         avg_s = ms_tot / cnt / 1e3
         if name in ("qp_lu", "qp_lu_pivot"):
@@ -231,6 +265,7 @@ def run_nlp(args, world, rank, local_rank):
         roof["traffic"] = _load_pmc(name + "@cfg6")
         roof["avg_launch_ms"] = round(avg_s * 1e3, 4)
         roof["phases_ms_per_step"] = {k.replace("qp_", "nlp_"): v for k, v in breakdown.items()}
+    if rank == 0:
         line = {
             "metric": "NLP KKT sensitivity solves/sec (fwd+rev)"
                       + (" [separate forward and reverse calls]" if args.nlp_separate else ""),
@@ -379,7 +414,7 @@ def run_conic(args, world, rank, local_rank):
     # initialises HIP (config 5 extrapolates with the engine's iteration
     # counts, a host computation done after the GPU run)
     cpu_raw = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu_baseline(args, world, rank):
         workers = cpu_workers(args)
         cpu_raw = conic_cpu_samples(args.config, args.cpu_seconds, workers, variant)
     torch.cuda.set_device(local_rank)
@@ -398,20 +433,22 @@ def run_conic(args, world, rank, local_rank):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    # iteration counts (deterministic for fixed inputs) for the byte count
-    eng.forward_reverse(dev["dx"], db=dev["db"], dc=dev["dc"], want_dA=False)
-    stats = eng.lsqr_stats()
-    it_f = stats["fwd_iterations"].astype(np.float64)
-    it_r = stats["iterations"].astype(np.float64)
-    torch.cuda.synchronize()
-    eng.phase_times()
-    eng.set_profiling(True)
+    if args.full:
+        # iteration counts (deterministic for fixed inputs) for the byte count
+        eng.forward_reverse(dev["dx"], db=dev["db"], dc=dev["dc"], want_dA=False)
+        stats = eng.lsqr_stats()
+        it_f = stats["fwd_iterations"].astype(np.float64)
+        it_r = stats["iterations"].astype(np.float64)
+        torch.cuda.synchronize()
+        eng.phase_times()
+        eng.set_profiling(True)
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     if dist:
         dist.barrier()
@@ -422,8 +459,10 @@ def run_conic(args, world, rank, local_rank):
         tt = torch.tensor([elapsed], dtype=torch.float64, device="cuda")
         dist.all_reduce(tt, op=dist.ReduceOp.MAX)
         elapsed = float(tt.item())
-    if rank == 0:
-        cpu = None
+    if rank == 0 and args.dump_outputs and last is not None:
+        dump_outputs(args.dump_outputs, {"forward": last[0], "reverse": last[1]})
+    cpu = roof = None
+    if rank == 0 and args.full:
         if cpu_raw is not None:
             cpu = conic_cpu_baseline(args.config, args.cpu_seconds, cpu_raw,
                                      float(it_f.mean() + it_r.mean()), variant)
@@ -460,6 +499,7 @@ def run_conic(args, world, rank, local_rank):
                     lsqr_istop={"forward": {str(k): int(v) for k, v in zip(*np.unique(stats["fwd_istop"], return_counts=True))},
                                 "reverse": {str(k): int(v) for k, v in zip(*np.unique(stats["istop"], return_counts=True))}},
                     phases_ms_per_step={k: round(v[0] / args.steps, 4) for k, v in sorted(phases.items())})
+    if rank == 0:
         value = world * B * args.steps / elapsed
         print(json.dumps({
             "metric": "KKT sensitivity solves/sec (fwd+rev) on batched conic programs",
@@ -517,7 +557,7 @@ def run_sparse(args, world, rank, local_rank):
     c = SPARSE_CFG[args.config]
     B = args.batch or c["batch"]
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu_baseline(args, world, rank):
         cpu = _sparse_cpu(args.config, min(args.cpu_seconds, 20.0))
     torch.cuda.set_device(local_rank)
     from diffopt_amd import synthetic as syn
@@ -572,23 +612,33 @@ def run_sparse(args, world, rank, local_rank):
     for _ in range(args.warmup):
         step()
     torch.cuda.synchronize()
-    if args.config == 7:
-        st = eng.lsqr_stats()
-        it_f, it_r = st[:, 1, 1].astype(np.float64), st[:, 0, 1].astype(np.float64)
-    else:
-        st = eng.lsqr_stats()
-        it_f, it_r = st["fwd_iterations"].astype(np.float64), st["iterations"].astype(np.float64)
-    eng.phase_times()
-    eng.set_profiling(True, phases=[phase])
+    if args.full:
+        if args.config == 7:
+            st = eng.lsqr_stats()
+            it_f, it_r = st[:, 1, 1].astype(np.float64), st[:, 0, 1].astype(np.float64)
+        else:
+            st = eng.lsqr_stats()
+            it_f, it_r = st["fwd_iterations"].astype(np.float64), st["iterations"].astype(np.float64)
+        eng.phase_times()
+        eng.set_profiling(True, phases=[phase])
     torch.cuda.synchronize()
     t0 = time.perf_counter()
+    last = None
     for _ in range(args.steps):
-        step()
+        last = step()
     torch.cuda.synchronize()
     elapsed = time.perf_counter() - t0
     eng.set_profiling(False)
-    ms_tot, cnt = eng.phase_times()[phase]
-    if rank == 0:
+    if rank == 0 and args.dump_outputs and last is not None:
+        if args.config == 7:
+            dump_outputs(args.dump_outputs, {"reverse": last[0], "forward": last[1]})
+        else:
+            (fo, fdx), (g, _, rdb, rdc) = last
+            dump_outputs(args.dump_outputs, {"forward": fo, "forward_dx": fdx, "reverse": g,
+                                             "reverse_db": rdb, "reverse_dc": rdc})
+    roof = None
+    if rank == 0 and args.full:
+        ms_tot, cnt = eng.phase_times()[phase]
         avg_s = ms_tot / cnt / 1e3
         per_step = b_it * float((it_f + it_r).sum())
         achieved = per_step / (ms_tot / 1e3 / args.steps) / 1e9
@@ -597,6 +647,7 @@ def run_sparse(args, world, rank, local_rank):
                     kernel=phase,
                     avg_launch_ms=round(avg_s * 1e3, 4), bytes_per_iteration=b_it, nnz_per_problem=nnz,
                     lsqr_iterations_mean={"forward": float(it_f.mean()), "reverse": float(it_r.mean())})
+    if rank == 0:
         print(json.dumps({
             "metric": "KKT sensitivity solves/sec (fwd+rev), sparse route",
             "value": round(world * B * args.steps / elapsed, 3), "unit": "solves/s", "n_gpus": world,
@@ -682,7 +733,7 @@ def make_qp_step(eng, d, out_rev, out_fwd, gather, B, pipe=None):
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--gpus", type=int, default=1)
-    ap.add_argument("--steps", type=int, default=20)
+    ap.add_argument("--steps", type=int, default=20, help="timed steps (at least 1)")
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--config", type=int, default=None,
                     choices=sorted(QP_CFG) + sorted(CONIC_CFG) + sorted(NLP_CFG) + sorted(SPARSE_CFG),
@@ -695,7 +746,13 @@ def main():
                     help="CPU-baseline processes (default: every usable host core, host_cores())")
     ap.add_argument("--conic-variant", choices=["bench", "wellcond"], default="bench",
                     help="config 4: the bench generator (LSQR stops at maxiter) or the converging variant")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="also measure the roofline (untimed per-phase pass + the dominant kernel timed live "
+                         "with HIP events) and the CPU baseline; off: both are null in the result line")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None,
+                    help="write the arrays the last timed step returned as DIR/<name>.npy (float64, at most "
+                         "64 MB together; the inputs are seeded and identical from run to run)")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--nlp-separate", action="store_true",
                     help="config 6: time dopt_nlp_forward and dopt_nlp_reverse as two calls (the reference's "
                          "pattern) instead of the fused dopt_nlp_forward_reverse")
@@ -703,8 +760,10 @@ def main():
     ap.add_argument("--sync-allgather", action="store_true",
                     help="N > 1: blocking all-gather per step instead of the overlapped pipeline")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
-    world = int(os.environ.get("WORLD_SIZE", "1"))
+    world =int(os.environ.get("WORLD_SIZE", "1"))
     rank = int(os.environ.get("RANK", "0"))
     local_rank = int(os.environ.get("LOCAL_RANK", "0"))
     if args.config is None:
@@ -722,7 +781,7 @@ def main():
     B, n, m, p = cfg["batch"], cfg["n"], cfg["m"], cfg["p"]
 
     cpu = None
-    if rank == 0 and world == 1 and not args.no_cpu_baseline:
+    if want_cpu_baseline(args, world, rank):
         workers = cpu_workers(args)
         cpu = cpu_baseline(cfg, args.cpu_seconds, workers)
 
@@ -758,12 +817,10 @@ def main():
     if pipe is not None:
         pipe.drain()
     torch.cuda.synchronize()
-    sizes = eng.system_size()
-    kinds = eng.lu_kind()
-    symr = eng.sym_route()
-    breakdown, name = _phase_breakdown(eng, step, 3, pipe.drain if pipe is not None else None)
-    eng.phase_times()                      # reset accumulators
-    eng.set_profiling(True, phases=[name])
+    if args.full:
+        breakdown, name = _phase_breakdown(eng, step, 3, pipe.drain if pipe is not None else None)
+        eng.phase_times()                      # reset accumulators
+        eng.set_profiling(True, phases=[name])
     if dist:
         dist.barrier()
     torch.cuda.synchronize()
@@ -785,13 +842,19 @@ def main():
         elapsed = float(tt.item())
     if (eng.info() != 0).any():
         raise RuntimeError("singular KKT in the benchmark batch")
+    sizes = eng.system_size()
+    kinds = eng.lu_kind()
+    symr = eng.sym_route()
+    Ns = sizes.astype("float64")
+    if rank == 0 and args.dump_outputs:
+        dump_outputs(args.dump_outputs, {"reverse": out_rev, "forward": out_fwd})
 
-    if rank == 0:
+    roof = None
+    if rank == 0 and args.full:
         # dominant kernel and its roofline (algorithmic work per launch ÷ avg
         # launch time measured with HIP events on the engine's stream)
         ms_tot, cnt = phases[name]   # live, over the timed region
         avg_s = ms_tot / cnt / 1e3
-        Ns = sizes.astype("float64")
         if name in ("qp_lu", "qp_lu_pivot"):
             # flops the shipped factorisation does: N'³/3 per problem on the
             # P-symmetric route (lower trailing tiles, U from L), 2N'³/3 on the
@@ -834,6 +897,7 @@ def main():
                             fp64_ms=round(1e3 * t_fp, 4), bytes=b_step, flops=f_step,
                             frac=round(max(t_hbm, t_fp) / ms_step, 4),
                             reference_flops=f_ref, fp64_ms_at_reference_flops=round(1e3 * f_ref / (PEAK_FP64_TFLOPS * 1e12), 4))
+    if rank == 0:
         value = world * B * args.steps / elapsed
         line = {
             "metric": "KKT sensitivity solves/sec (fwd+rev) on batched QPs",

@@ -8,6 +8,8 @@
 #   tools/gpu_job.sh prof  TAG [bench.py args]    rocprofv3 --kernel-trace --stats → gpurun_out/prof_TAG/
 #   tools/gpu_job.sh pmc   TAG [bench.py args]    FETCH_SIZE and WRITE_SIZE, one pass each
 #                                                 → gpurun_out/pmc_TAG.json (tools/pmc_summary.py)
+# A bench line carries `roofline` and `cpu_baseline` only with --full among the
+# bench.py args (--full --no-cpu-baseline: the roofline alone).
 # Steps can be chained in one gpurun call with &&.  Environment overrides
 # (e.g. DOPT_LU=0) are passed through.
 set -o pipefail
