@@ -175,7 +175,7 @@ int dopt_destroy(dopt_handle* h) {
     (void)hipStreamDestroy(h->crit);
   }
   DevBuf* bufs[] = {&h->dinv, &h->plist, &h->lsqr_ws, &h->binv, &h->fwdw, &h->K, &h->ipiv, &h->s, &h->kidx, &h->meta, &h->rhs,
-                    &h->x, &h->cone_dev, &h->vp, &h->dpi, &h->cwork, &h->cinfo, &h->cnorm, &h->csplit, &h->krhs, &h->kx,
+                    &h->x, &h->cone_dev, &h->vp, &h->dpi, &h->cwork, &h->cinfo, &h->cnorm, &h->cinfok, &h->csplit, &h->krhs, &h->kx,
                     &h->kfull, &h->kamax, &h->nlp_map, &h->nlp_shift, &h->nlp_scale, &h->kls, &h->gk, &h->glist,
                     &h->mws, &h->qsy, &h->psd_eig, &h->psd_app, &h->ukp, &h->nlp_rd, &h->nlp_ri, &h->nlp_t1, &h->nlp_t2,
                     &h->nlp_msc, &h->pack, &h->tpack, &h->rpack};
@@ -1403,6 +1403,7 @@ static void conic_set_common(Handle* h, const double* A, const double* b, const 
   h->cy = stage_in(*h, h->own_cin[5], y, B * m);
   h->cset = true;
   h->cfactored = false;
+  h->conic_k = 0;
   DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
 }
 
@@ -1474,6 +1475,7 @@ int dopt_conic_forward(dopt_handle* h, const double* dA, const double* db, const
                        double* out, double* out_dx) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_forward on a non-conic handle");
+    h->conic_k = 0;
     if (!out) throw Error(-1, "out is required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
@@ -1496,6 +1498,7 @@ int dopt_conic_forward_reverse(dopt_handle* h, const double* dA, const double* d
                                double* out_db, double* out_dc) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_forward_reverse on a non-conic handle");
+    h->conic_k = 0;
     if (!out || !dx || !out_g) throw Error(-1, "out, dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
@@ -1559,6 +1562,7 @@ int dopt_conic_reverse(dopt_handle* h, const double* dx, double* out_g, double* 
                        double* out_db, double* out_dc) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_reverse on a non-conic handle");
+    h->conic_k = 0;
     if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
@@ -1574,6 +1578,70 @@ int dopt_conic_reverse(dopt_handle* h, const double* dx, double* out_g, double* 
     copy_out(*h, out_dc, oc, B * n);
     DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
     h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_conic_reverse_k(dopt_handle* h, int32_t k, const double* dx, double* out_g, double* out_dA,
+                         double* out_db, double* out_dc) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_reverse_k on a non-conic handle");
+    h->conic_k = 0;
+    if (k < 1) throw Error(-1, "dopt_conic_reverse_k: k must be at least 1");
+    if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1, K = (size_t)k;
+    const double* d = stage_in(*h, h->tin[0], dx, K * B * n);
+    double* og = out_ptr(*h, h->tout[2], out_g, K * B * N);
+    double* oA = out_ptr(*h, h->tout[3], out_dA, K * B * m * n);
+    double* ob = out_ptr(*h, h->tout[4], out_db, K * B * m);
+    double* oc = out_ptr(*h, h->tout[5], out_dc, K * B * n);
+    dopt::conic_reverse_k(*h, k, d, og, oA, ob, oc);
+    copy_out(*h, out_g, og, K * B * N);
+    copy_out(*h, out_dA, oA, K * B * m * n);
+    copy_out(*h, out_db, ob, K * B * m);
+    copy_out(*h, out_dc, oc, K * B * n);
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->conic_k = k;
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const double* db, const double* dc,
+                         double* out, double* out_dx) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_forward_k on a non-conic handle");
+    h->conic_k = 0;
+    if (k < 1) throw Error(-1, "dopt_conic_forward_k: k must be at least 1");
+    if (!out) throw Error(-1, "out is required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1, K = (size_t)k;
+    const double* a = stage_in(*h, h->tin[1], dA, K * B * m * n);
+    const double* b = stage_in(*h, h->tin[2], db, K * B * m);
+    const double* c = stage_in(*h, h->tin[3], dc, K * B * n);
+    double* o = out_ptr(*h, h->tout[0], out, K * B * N);
+    double* ox = out_ptr(*h, h->tout[1], out_dx, K * B * n);
+    dopt::conic_forward_k(*h, k, a, b, c, o, ox);
+    copy_out(*h, out, o, K * B * N);
+    copy_out(*h, out_dx, ox, K * B * n);
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->conic_k = k;
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_conic_lsqr_stats_k(dopt_handle* h, int32_t k, int32_t* stats) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_lsqr_stats_k on a non-conic handle");
+    if (!stats) throw Error(-1, "stats is required");
+    if (k < 1) throw Error(-1, "dopt_conic_lsqr_stats_k: k must be at least 1");
+    if (h->conic_k != k || !h->cinfok.p)
+      throw Error(-1, "dopt_conic_lsqr_stats_k: the last conic call was not a _k call with this k");
+    DOPT_CHECK_HIP(hipMemcpyAsync(stats, h->cinfok.p, (size_t)2 * h->batch * k * sizeof(int32_t),
+                                  hipMemcpyDeviceToHost, h->stream));
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
     return 0;
   });
 }

@@ -1239,6 +1239,363 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
   }
 }
 
+// ---------------------------------------------------------------------------
+// Multi-seed LSQR (dopt_conic_reverse_k / dopt_conic_forward_k): up to G
+// same-direction sequences of one problem in one workgroup, in lockstep, every
+// M / Mᵀ apply of the live ones sharing one sweep over A (gemv_multi<1..G>).
+// grid (problems, ⌈k / G⌉): workgroup (b, y) runs seeds y·G … of problem b;
+// workspace, right-hand side and solution of (seed j, problem b) are block
+// j·B + b, info is [istop (B) | iterations (B)] per seed.  Each sequence keeps
+// its own scalars, stopping tests and iteration count as in
+// conic_lsqr2_kernel; the scalars live in LDS (SeqState) and the sequences of
+// each sweep are listed there (live ones, compacted), so a sweep serves
+// exactly the sequences that need the product and a stopped sequence is never
+// touched again.  Every product keeps the single-sequence summation order
+// (same PAIR_K and wave count; the column chunk only groups loads): each
+// seed's solution, istop and iteration count are bit-identical to a
+// conic_lsqr_kernel run of that seed alone.
+// ---------------------------------------------------------------------------
+#ifndef DOPT_PAIR_NCK
+#define DOPT_PAIR_NCK 3   // columns in flight per wave for three and more sequences (config 4, k = 4, 50 iterations: 1 → 54.6, 2 → 40.7, 3 → 38.3 ms; 4 → 37.6 beside 3 → 38.0 ms on another device, 48 more registers)
+#endif
+constexpr int LSQRK_G = 4;   // widest group: ya + wr of gemv_multi<4> are 128 VGPRs, ys 64 KB of LDS
+
+struct SeqState {
+  double alpha, beta, anorm, ddnorm, res2, xxnorm, zz, sn2, cs2, rhobar, phibar, bnorm;
+  double fin0, fin1, fin2, fin3;   // terminal rnorm, arnorm, xnorm, anorm
+  int it, istop, live, mt;
+};
+// member-wise copies between LDS and registers (an aggregate copy keeps part of the struct on the stack)
+#define DOPT_SEQ_COPY(D, S_)                                                                              \
+  do {                                                                                                    \
+    (D).alpha = (S_).alpha; (D).beta = (S_).beta; (D).anorm = (S_).anorm; (D).ddnorm = (S_).ddnorm;       \
+    (D).res2 = (S_).res2; (D).xxnorm = (S_).xxnorm; (D).zz = (S_).zz; (D).sn2 = (S_).sn2;                 \
+    (D).cs2 = (S_).cs2; (D).rhobar = (S_).rhobar; (D).phibar = (S_).phibar; (D).bnorm = (S_).bnorm;       \
+    (D).fin0 = (S_).fin0; (D).fin1 = (S_).fin1; (D).fin2 = (S_).fin2; (D).fin3 = (S_).fin3;               \
+    (D).it = (S_).it; (D).istop = (S_).istop; (D).live = (S_).live; (D).mt = (S_).mt;                     \
+  } while (0)
+
+struct SeqVec {
+  double *x, *u, *vv, *w, *tmp, *s1, *s2, *s4;
+};
+__device__ __forceinline__ SeqVec seq_vec(double* base, int N, int m) {
+  SeqVec V;
+  V.x = base;
+  V.u = V.x + N;
+  V.vv = V.u + N;
+  V.w = V.vv + N;
+  V.tmp = V.w + N;
+  V.s1 = V.tmp + N;
+  V.s2 = V.s1 + m;
+  V.s4 = V.s2 + 2 * (size_t)m;
+  return V;
+}
+
+__device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
+
+// the A products of the NV listed sequences from one sweep; dir 0: M·v
+// (x = v_n, w = Dv), 1: Mᵀ·u (x = u_n, w = u_m); y → s2, g → s4
+template <int NV>
+__device__ __forceinline__ void sweep_list(const ConicProblem& pr, double* wb0, size_t qs, const int* lst, int dir,
+                                           double* ys) {
+  const int n = pr.n, m = pr.m, N = n + m + 1;
+  const double* xs[NV];
+  const double* ws[NV];
+  double* yv[NV];
+  double* gv[NV];
+#pragma unroll
+  for (int c = 0; c < NV; ++c) {
+    const SeqVec V = seq_vec(wb0 + (size_t)uniform(lst[c]) * qs, N, m);
+    xs[c] = dir == 0 ? V.vv : V.u;
+    ws[c] = dir == 0 ? V.s1 : V.u + n;
+    yv[c] = V.s2;
+    gv[c] = V.s4;
+  }
+  if constexpr (NV <= 2) gemv_multi<NV>(pr.A, m, m, n, xs, ws, yv, gv, ys);
+  else gemv_multi<NV, PAIR_K, DOPT_PAIR_NCK>(pr.A, m, m, n, xs, ws, yv, gv, ys);
+}
+
+template <int G>
+__device__ __forceinline__ void sweep_live(const ConicProblem& pr, double* wb0, size_t qs, const int* lst, int cnt,
+                                           int dir, double* ys) {
+  if (cnt == 1) sweep_list<1>(pr, wb0, qs, lst, dir, ys);
+  else if (cnt == 2) sweep_list<2>(pr, wb0, qs, lst, dir, ys);
+  if constexpr (G >= 4) {
+    if (cnt == 3) sweep_list<3>(pr, wb0, qs, lst, dir, ys);
+    else if (cnt == 4) sweep_list<4>(pr, wb0, qs, lst, dir, ys);
+  }
+}
+
+// tmp = M·vv of the cnt listed sequences (each sequence's arithmetic as M_apply)
+template <int G>
+__device__ __forceinline__ void M_applyK(const ConicProblem& pr, const ConeDesc* cones, int ncones, double* wb0,
+                                         size_t qs, const int* lst, int cnt, double* lds, double* red, double* ys) {
+  const int n = pr.n, m = pr.m, N = n + m + 1, t = threadIdx.x;
+  for (int c = 0; c < cnt; ++c) {
+    const SeqVec V = seq_vec(wb0 + (size_t)uniform(lst[c]) * qs, N, m);
+    dpi_apply(cones, ncones, pr.v, pr.P, V.vv + n, V.s1, 0, lds, red, nullptr);
+  }
+  sweep_live<G>(pr, wb0, qs, lst, cnt, 0, ys);
+  for (int c = 0; c < cnt; ++c) {
+    const SeqVec V = seq_vec(wb0 + (size_t)uniform(lst[c]) * qs, N, m);
+    const double* z = V.vv;
+    double* out = V.tmp;
+    const double w = z[n + m];
+    double cu = 0.0, bd = 0.0;
+    for (int j = t; j < n; j += CTPB) {
+      out[j] = -V.s4[j] + pr.c[j] * w;
+      cu = fma(pr.c[j], z[j], cu);
+    }
+    for (int i = t; i < m; i += CTPB) {
+      out[n + i] = V.s2[i] + z[n + i] - V.s1[i] + pr.b[i] * w;
+      bd = fma(pr.b[i], V.s1[i], bd);
+    }
+    const double s = cblock_sum(-cu - bd, red);
+    if (t == 0) out[n + m] = s;
+    __syncthreads();
+  }
+}
+
+// Mᵀ·u of the cnt listed sequences into vv (first: the start of the
+// bidiagonalisation) or tmp (each sequence's arithmetic as MT_apply)
+template <int G>
+__device__ __forceinline__ void MT_applyK(const ConicProblem& pr, const ConeDesc* cones, int ncones, double* wb0,
+                                          size_t qs, const int* lst, int cnt, bool first, double* lds, double* red,
+                                          double* ys) {
+  const int n = pr.n, m = pr.m, N = n + m + 1, t = threadIdx.x;
+  sweep_live<G>(pr, wb0, qs, lst, cnt, 1, ys);
+  for (int c = 0; c < cnt; ++c) {
+    const SeqVec V = seq_vec(wb0 + (size_t)uniform(lst[c]) * qs, N, m);
+    const double* r = V.u;
+    double* out = first ? V.vv : V.tmp;
+    const double tw = r[n + m];
+    for (int i = t; i < m; i += CTPB) V.s1[i] = -V.s2[i] - r[n + i] - pr.b[i] * tw;
+    __syncthreads();
+    dpi_apply(cones, ncones, pr.v, pr.P, V.s1, out + n, 1, lds, red, nullptr);
+    double cp = 0.0, bq = 0.0;
+    for (int j = t; j < n; j += CTPB) {
+      out[j] = V.s4[j] - pr.c[j] * tw;
+      cp = fma(pr.c[j], r[j], cp);
+    }
+    for (int i = t; i < m; i += CTPB) {
+      out[n + i] += r[n + i];
+      bq = fma(pr.b[i], r[n + i], bq);
+    }
+    const double s = cblock_sum(cp + bq, red);
+    if (t == 0) out[n + m] = s;
+    __syncthreads();
+  }
+}
+
+// lst ← the sequences q < ng with S[q].live (and, with_mt, S[q].mt), in
+// order; returns their count (workgroup-uniform).  Barriers on both sides:
+// S as written before the call is what the list is built from.
+template <int G>
+__device__ __forceinline__ int list_live(const SeqState* S, int ng, bool with_mt, int* lst, int* lcnt) {
+  __syncthreads();
+  if (threadIdx.x == 0) {
+    int c = 0;
+    for (int q = 0; q < ng; ++q)
+      if (S[q].live && (!with_mt || S[q].mt)) lst[c++] = q;
+    *lcnt = c;
+  }
+  __syncthreads();
+  return uniform(*lcnt);
+}
+
+template <int G>
+__global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
+    const ConeDesc* __restrict__ cones_g, int ncones, const double* __restrict__ A,
+    const double* __restrict__ b, const double* __restrict__ c,
+    const double* __restrict__ v, const double* __restrict__ P, int plen, int m, int n, int k,
+    const double* __restrict__ rhs, double rhs_zero_tol, double* __restrict__ work,
+    double* __restrict__ xout, int32_t* __restrict__ info, double* __restrict__ norms0, int maxiter) {
+  static_assert(G == 2 || G == 4, "sweep_live dispatches on 1..2 or 1..4 live sequences");
+  extern __shared__ __attribute__((aligned(16))) double lds[];
+  __shared__ double red[4];
+  __shared__ ConeDesc cones[128];
+  __shared__ double ys[G * 4 * PAIR_ROWS];
+  __shared__ SeqState S[G];
+  __shared__ int lstL[G], lstT[G], lcnt;
+  const int bidx = blockIdx.x, B = gridDim.x, t = threadIdx.x;
+  const int seed0 = blockIdx.y * G;
+  const int ng = min(G, k - seed0);   // this group's sequences: seeds seed0 … seed0 + ng − 1
+  const int N = n + m + 1;
+  const ConeDesc* cn = cones_g;
+  if (ncones <= 128) {
+    for (int q = t; q < ncones; q += CTPB) cones[q] = cones_g[q];
+    cn = cones;
+  }
+  ConicProblem pr;
+  pr.A = A + (size_t)bidx * m * n;
+  pr.b = b + (size_t)bidx * m;
+  pr.c = c + (size_t)bidx * n;
+  pr.v = v + (size_t)bidx * m;
+  pr.P = P + (size_t)bidx * plen;
+  pr.m = m;
+  pr.n = n;
+  const size_t wl = (size_t)5 * N + 3 * (size_t)m + n;
+  const size_t qs = (size_t)B * wl;                          // workspace stride between seeds
+  double* wb0 = work + ((size_t)seed0 * B + bidx) * wl;      // sequence q of the group: wb0 + q·qs
+  for (int q = 0; q < ng; ++q) {
+    const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
+    const double* rb = rhs + ((size_t)(seed0 + q) * B + bidx) * N;
+    double bb = 0.0;
+    for (int i = t; i < N; i += CTPB) {
+      const double r = rb[i];
+      V.u[i] = r;
+      V.x[i] = 0.0;
+      bb = fma(r, r, bb);
+    }
+    const double beta = sqrt(cblock_sum(bb, red));
+    const bool go = beta > rhs_zero_tol;
+    if (go)
+      for (int i = t; i < N; i += CTPB) V.u[i] /= beta;
+    if (t == 0) {
+      SeqState Q;
+      Q.alpha = Q.anorm = Q.ddnorm = Q.res2 = Q.xxnorm = Q.zz = Q.sn2 = Q.cs2 = Q.rhobar = Q.phibar = Q.bnorm = 0.0;
+      Q.fin0 = Q.fin1 = Q.fin2 = Q.fin3 = 0.0;
+      Q.it = Q.istop = Q.mt = 0;
+      Q.beta = beta;
+      Q.live = go;   // until α is known: takes part in the first Mᵀ·u
+      DOPT_SEQ_COPY(S[q], Q);
+    }
+  }
+  int cnt = list_live<G>(S, ng, false, lstL, &lcnt);
+  if (cnt) MT_applyK<G>(pr, cn, ncones, wb0, qs, lstL, cnt, true, lds, red, ys);
+  for (int cc = 0; cc < cnt; ++cc) {
+    const int q = uniform(lstL[cc]);
+    const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
+    SeqState Q;
+    DOPT_SEQ_COPY(Q, S[q]);
+    double aa = 0.0;
+    for (int i = t; i < N; i += CTPB) aa = fma(V.vv[i], V.vv[i], aa);
+    Q.alpha = sqrt(cblock_sum(aa, red));
+    Q.live = 0;
+    if (Q.alpha > 0.0) {
+      for (int i = t; i < N; i += CTPB) { V.vv[i] /= Q.alpha; V.w[i] = V.vv[i]; }
+      __syncthreads();
+      Q.anorm = Q.ddnorm = Q.res2 = Q.xxnorm = Q.zz = 0.0;
+      Q.sn2 = 0.0;
+      Q.cs2 = -1.0;
+      Q.rhobar = Q.alpha;
+      Q.phibar = Q.beta;
+      Q.bnorm = Q.beta;
+      Q.live = maxiter > 0;
+    }
+    if (t == 0) DOPT_SEQ_COPY(S[q], Q);
+  }
+  const double eps = 2.220446049250313e-16;
+  const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
+  while (true) {
+    cnt = list_live<G>(S, ng, false, lstL, &lcnt);
+    if (cnt == 0) break;
+    // M·v of the live sequences
+    M_applyK<G>(pr, cn, ncones, wb0, qs, lstL, cnt, lds, red, ys);
+    for (int cc = 0; cc < cnt; ++cc) {
+      const int q = uniform(lstL[cc]);
+      const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
+      SeqState Q;
+      DOPT_SEQ_COPY(Q, S[q]);
+      ++Q.it;
+      Q.mt = 0;
+      double su = 0.0;
+      for (int i = t; i < N; i += CTPB) { const double ui = V.tmp[i] - Q.alpha * V.u[i]; V.u[i] = ui; su = fma(ui, ui, su); }
+      Q.beta = sqrt(cblock_sum(su, red));
+      if (Q.beta > 0.0) {
+        for (int i = t; i < N; i += CTPB) V.u[i] /= Q.beta;
+        __syncthreads();
+        Q.anorm = sqrt(Q.anorm * Q.anorm + Q.alpha * Q.alpha + Q.beta * Q.beta);
+        Q.mt = 1;
+      }
+      if (t == 0) DOPT_SEQ_COPY(S[q], Q);
+    }
+    // Mᵀ·u of those with β > 0
+    const int cntT = list_live<G>(S, ng, true, lstT, &lcnt);
+    if (cntT) MT_applyK<G>(pr, cn, ncones, wb0, qs, lstT, cntT, false, lds, red, ys);
+    for (int cc = 0; cc < cnt; ++cc) {
+      const int q = uniform(lstL[cc]);
+      const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
+      SeqState Q;
+      DOPT_SEQ_COPY(Q, S[q]);
+      if (Q.mt) {
+        double sv = 0.0;
+        for (int i = t; i < N; i += CTPB) { const double vi = V.tmp[i] - Q.beta * V.vv[i]; V.vv[i] = vi; sv = fma(vi, vi, sv); }
+        Q.alpha = sqrt(cblock_sum(sv, red));
+        if (Q.alpha > 0.0) for (int i = t; i < N; i += CTPB) V.vv[i] /= Q.alpha;
+        __syncthreads();
+      }
+      const double rhobar1 = Q.rhobar;
+      const double rho = hypot(rhobar1, Q.beta);
+      const double cs = rhobar1 / rho, sn = Q.beta / rho;
+      const double theta = sn * Q.alpha;
+      Q.rhobar = -cs * Q.alpha;
+      const double phi = cs * Q.phibar;
+      Q.phibar = sn * Q.phibar;
+      const double tau = sn * phi;
+      const double t1 = phi / rho, t2 = -theta / rho;
+      double sw = 0.0;
+      for (int i = t; i < N; i += CTPB) {
+        const double wi = V.w[i];
+        sw = fma(wi, wi, sw);
+        V.x[i] = V.x[i] + t1 * wi;
+        V.w[i] = V.vv[i] + t2 * wi;
+      }
+      Q.ddnorm += cblock_sum(sw, red) / (rho * rho);
+      const double delta = Q.sn2 * rho, gambar = -Q.cs2 * rho;
+      const double rhs_ = phi - delta * Q.zz;
+      const double zbar = rhs_ / gambar;
+      const double xnorm = sqrt(Q.xxnorm + zbar * zbar);
+      const double gamma = hypot(gambar, theta);
+      Q.cs2 = gambar / gamma;
+      Q.sn2 = theta / gamma;
+      Q.zz = rhs_ / gamma;
+      Q.xxnorm += Q.zz * Q.zz;
+      const double acond = Q.anorm * sqrt(Q.ddnorm);
+      const double rnorm = sqrt(Q.phibar * Q.phibar + Q.res2);
+      const double arnorm = Q.alpha * fabs(tau);
+      const double test1 = rnorm / Q.bnorm;
+      const double test2 = (Q.anorm * rnorm != 0.0) ? arnorm / (Q.anorm * rnorm) : 0.0;
+      const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
+      const double t1r = test1 / (1.0 + Q.anorm * xnorm / Q.bnorm);
+      const double rtol = btol + atol * Q.anorm * xnorm / Q.bnorm;
+      Q.fin0 = rnorm;
+      Q.fin1 = arnorm;
+      Q.fin2 = xnorm;
+      Q.fin3 = Q.anorm;
+      int istop = 0;
+      if (Q.it >= maxiter) istop = 7;
+      if (1.0 + test3 <= 1.0) istop = 6;
+      if (1.0 + test2 <= 1.0) istop = 5;
+      if (1.0 + t1r <= 1.0) istop = 4;
+      if (test3 <= ctol) istop = 3;
+      if (test2 <= atol) istop = 2;
+      if (test1 <= rtol) istop = 1;
+      Q.istop = istop;
+      __syncthreads();
+      if (istop) Q.live = 0;
+      if (t == 0) DOPT_SEQ_COPY(S[q], Q);
+    }
+  }
+  __syncthreads();
+  for (int q = 0; q < ng; ++q) {
+    const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
+    double* xo = xout + ((size_t)(seed0 + q) * B + bidx) * N;
+    for (int i = t; i < N; i += CTPB) xo[i] = V.x[i];
+    if (t == 0 && info) {
+      info[((size_t)2 * (seed0 + q)) * B + bidx] = S[q].istop;
+      info[((size_t)2 * (seed0 + q) + 1) * B + bidx] = S[q].it;
+    }
+    if (seed0 + q == 0 && t == 0 && norms0) {
+      double* nb = norms0 + (size_t)4 * bidx;
+      nb[0] = S[0].fin0;
+      nb[1] = S[0].fin1;
+      nb[2] = S[0].fin2;
+      nb[3] = S[0].fin3;
+    }
+  }
+}
+
 // forward RHS: [dA_moiᵀ vp + dc; −dA_moi x + db; −dc·x − db·vp]  (ConicProgram.jl:314-318)
 __global__ __launch_bounds__(CTPB) void conic_fwd_rhs_kernel(
     const double* __restrict__ dA, const double* __restrict__ db, const double* __restrict__ dc,
@@ -2723,6 +3080,122 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
     hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g, h.cx,
                        h.vp.as<double>() + (size_t)B * m, m, n, out_dA, out_db, out_dc);
   ccheck();
+}
+
+// ---------------------------------------------------------------------------
+// k seeds per problem (dopt_conic_reverse_k / dopt_conic_forward_k), seed-major:
+// seed j's vectors are the batch block at j·B·len.  Dense persistent route:
+// all k right-hand sides, one conic_lsqrk_kernel launch (groups of LSQRK_G
+// seeds per workgroup sharing each sweep over A), the outputs per seed.  Split
+// and sparse routes, and k = 1: the single-seed call per seed (no shared sweep
+// there yet).  Per-seed [istop | iterations] in cinfok; the single-call info and
+// norms (cinfo, cnorm) end as seed 0's.
+// ---------------------------------------------------------------------------
+// (one seed: the single-sequence kernel, two workgroups per CU where the group kernel's registers allow one)
+static bool multi_shared_sweep(const Handle& h, int k) { return k > 1 && !h.sparse && !use_split(h); }
+
+static void keep_seed_info(Handle& h, int j) {
+  const size_t B = h.batch;
+  DOPT_CHECK_HIP(hipMemcpyAsync(h.cinfok.as<int32_t>() + (size_t)j * 2 * B, h.cinfo.p, 2 * B * sizeof(int32_t),
+                                hipMemcpyDeviceToDevice, h.stream));
+}
+
+// rhs: k·B right-hand sides behind the k·B workspaces of cwork (sized by the caller)
+static void conic_lsqr_k(Handle& h, int k, double tol, const double* rhs, double* out) {
+  const int B = (int)h.batch, m = h.m, n = h.n;
+  const int nc = (int)h.cones.size() / 2;
+  h.cinfo.ensure((size_t)4 * std::max(B, 1) * sizeof(int32_t));
+  h.cnorm.ensure((size_t)8 * std::max(B, 1) * sizeof(double));
+  const size_t dl = dpi_lds_bytes(h.cones);
+  // static LDS of conic_lsqrk_kernel<G>: ys (G·4·PAIR_ROWS doubles), the cone table, the states and lists
+  auto fits = [&](int G) {
+    return (size_t)G * 4 * PAIR_ROWS * sizeof(double) + 128 * sizeof(ConeDesc) + G * sizeof(SeqState) + 256 + dl <=
+           (size_t)160 * 1024;
+  };
+  PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
+  auto go = [&](auto kern, int G) {
+    hipLaunchKernelGGL(kern, dim3(B, (k + G - 1) / G), dim3(CTPB), dl, h.stream, h.cone_dev.as<ConeDesc>(), nc, h.cA,
+                       h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(), h.dpi_len, m, n, k, rhs, tol,
+                       h.cwork.as<double>(), out, h.cinfok.as<int32_t>(), h.cnorm.as<double>(), lsqr_maxiter(h));
+  };
+  if (fits(LSQRK_G)) go(conic_lsqrk_kernel<LSQRK_G>, LSQRK_G);
+  else go(conic_lsqrk_kernel<2>, 2);   // PSD sides near PSD_MAX: their Dπ images leave LDS for two sequences' ys
+  ccheck();
+  // seed 0's [istop | iterations] where a single call leaves them (its norms: written there by the kernel)
+  DOPT_CHECK_HIP(hipMemcpyAsync(h.cinfo.p, h.cinfok.p, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToDevice,
+                                h.stream));
+}
+
+void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* out_dA, double* out_db,
+                     double* out_dc) {
+  if (k < 1) throw Error(-1, "dopt_conic_reverse_k: k must be at least 1");
+  if (!h.cfactored) conic_factor(h);
+  const int B = (int)h.batch, m = h.m, n = h.n;
+  const size_t N = (size_t)n + m + 1, Bz = (size_t)B;
+  h.cinfok.ensure((size_t)2 * std::max(B, 1) * k * sizeof(int32_t));
+  if (!multi_shared_sweep(h, k)) {
+    for (int j = k - 1; j >= 0; --j) {   // seed 0 last: the single-call info ends as its
+      conic_reverse(h, dx + j * Bz * n, out_g + j * Bz * N, out_dA ? out_dA + j * Bz * m * n : nullptr,
+                    out_db ? out_db + j * Bz * m : nullptr, out_dc ? out_dc + j * Bz * n : nullptr);
+      keep_seed_info(h, j);
+    }
+    return;
+  }
+  const size_t wl = 5 * N + 3 * (size_t)m + n;
+  h.cwork.ensure((size_t)k * Bz * (wl + N) * sizeof(double));
+  double* rhs = h.cwork.as<double>() + (size_t)k * Bz * wl;
+  {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
+    for (int j = 0; j < k; ++j)
+      hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx + j * Bz * n, h.cx, m, n,
+                         rhs + j * Bz * N);
+    ccheck();
+  }
+  conic_lsqr_k(h, k, 1e-4, rhs, out_g);   // per seed: `norm(dz) <= 1e-4` → g = 0 (ConicProgram.jl:369-370)
+  if (out_dA || out_db || out_dc) {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
+    for (int j = 0; j < k; ++j)
+      hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g + j * Bz * N, h.cx,
+                         h.vp.as<double>() + Bz * m, m, n, out_dA ? out_dA + j * Bz * m * n : nullptr,
+                         out_db ? out_db + j * Bz * m : nullptr, out_dc ? out_dc + j * Bz * n : nullptr);
+    ccheck();
+  }
+}
+
+void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const double* dc, double* out,
+                     double* out_dx) {
+  if (k < 1) throw Error(-1, "dopt_conic_forward_k: k must be at least 1");
+  if (!h.cfactored) conic_factor(h);
+  const int B = (int)h.batch, m = h.m, n = h.n;
+  const size_t N = (size_t)n + m + 1, Bz = (size_t)B;
+  h.cinfok.ensure((size_t)2 * std::max(B, 1) * k * sizeof(int32_t));
+  if (!multi_shared_sweep(h, k)) {
+    for (int j = k - 1; j >= 0; --j) {
+      conic_forward(h, dA ? dA + j * Bz * m * n : nullptr, db ? db + j * Bz * m : nullptr,
+                    dc ? dc + j * Bz * n : nullptr, out + j * Bz * N, out_dx ? out_dx + j * Bz * n : nullptr);
+      keep_seed_info(h, j);
+    }
+    return;
+  }
+  const size_t wl = 5 * N + 3 * (size_t)m + n;
+  h.cwork.ensure((size_t)k * Bz * (wl + N) * sizeof(double));
+  double* rhs = h.cwork.as<double>() + (size_t)k * Bz * wl;
+  {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
+    for (int j = 0; j < k; ++j)
+      hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA ? dA + j * Bz * m * n : nullptr,
+                         db ? db + j * Bz * m : nullptr, dc ? dc + j * Bz * n : nullptr, h.cx,
+                         h.vp.as<double>() + Bz * m, m, n, rhs + j * Bz * N);
+    ccheck();
+  }
+  conic_lsqr_k(h, k, 0.0, rhs, out);   // per seed: RHS == 0 → 0 (ConicProgram.jl:320)
+  if (out_dx) {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
+    for (int j = 0; j < k; ++j)
+      hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out + j * Bz * N, h.cx, m, n,
+                         out_dx + j * Bz * n);
+    ccheck();
+  }
 }
 
 }  // namespace dopt

@@ -232,6 +232,8 @@ struct Handle {
   std::vector<int32_t> cones;   // (code, dim) pairs
   DevBuf cone_dev;              // device copy of cone table (+ offsets)
   DevBuf vp, dpi, cwork, cinfo, cnorm;   // cnorm: LSQR terminal estimates, 8·B doubles
+  DevBuf cinfok;                // multi-seed calls: per seed [istop | iterations], 2·B·k int32
+  int32_t conic_k = 0;          // seeds of the last conic call if it was a _k call, else 0
   DevBuf csplit;                // split-path LSQR vectors, partial products, state
   int32_t conic_split = -1;     // -1 auto, 0 persistent kernel, 1 split (env DOPT_CONIC_SPLIT)
   int32_t lsqr_cap = 0;         // LSQR iteration cap (0: IterativeSolvers' maxiter = N; dopt_conic_set_maxiter)
@@ -464,6 +466,10 @@ void conic_reverse(Handle& h, const double* dx, double* out_g, double* out_dA,
 void conic_forward_reverse(Handle& h, const double* dA, const double* db, const double* dc, const double* dx,
                            double* out_f, double* out_dx, double* out_g, double* out_dA, double* out_db,
                            double* out_dc);
+void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* out_dA, double* out_db,
+                     double* out_dc);
+void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const double* dc, double* out,
+                     double* out_dx);
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 

@@ -72,6 +72,9 @@ SIGNATURES = {
     "dopt_conic_factor": (ctypes.c_int, [_h]),
     "dopt_conic_forward": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 5),
     "dopt_conic_reverse": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 5),
+    "dopt_conic_reverse_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 5),
+    "dopt_conic_forward_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 5),
+    "dopt_conic_lsqr_stats_k": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_void_p]),
     "dopt_nlp_set_structure": (ctypes.c_int, [_h, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int32]),
     "dopt_nlp_set": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 12),
@@ -111,7 +114,7 @@ def phase_mask(lib, names):
     return mask
 
 
-ABI_VERSION = 2
+ABI_VERSION = 3
 LU_KIND_LSQR, LU_KIND_NOPIV, LU_KIND_PIVOT, LU_KIND_SMALL = 0, 1, 2, 3
 
 

@@ -166,6 +166,57 @@ class ConicBatch:
             rA = rA.transpose(0, 2, 1) if not dev else rA.transpose(1, 2)
         return (out, fdx), (g, rA, rb, rc_)
 
+    def reverse_k(self, dx, want_dA=True):
+        """k seeds per solved cone program in one call (dopt_conic_reverse_k):
+        dx (k, B, n) → (g (k, B, N), dA (k, B, m, n) | None, db (k, B, m),
+        dc (k, B, n)); seed j bit-identical to ``reverse(dx[j])``.  On the
+        dense persistent route groups of seeds share each sweep over A."""
+        k = int(dx.shape[0])
+        B, n, m = self.batch, self.n, self.m
+        st = self._stage([dx])
+        dev = st.mem == _lib.DOPT_MEM_DEVICE
+        d = vector(dx, (k, B, n))
+        g = Staged.empty((k, B, self.N), dev)
+        dA = Staged.empty((k, B, n, m), dev) if want_dA else None   # column-major (m×n)
+        db = Staged.empty((k, B, m), dev)
+        dc = Staged.empty((k, B, n), dev)
+        rc = self.lib.dopt_conic_reverse_k(self.h, k, st.ptr(d), st.ptr(g), st.ptr(dA), st.ptr(db),
+                                           st.ptr(dc))
+        _lib.check(rc, self.h)
+        if dA is not None:
+            dA = dA.transpose(0, 1, 3, 2) if not dev else dA.transpose(2, 3)
+        return g, dA, db, dc
+
+    def forward_k(self, dA=None, db=None, dc=None):
+        """k tangents per problem (dopt_conic_forward_k): each given tangent
+        has a leading seed axis (k, B, …) → (out (k, B, N), dx (k, B, n));
+        seed j bit-identical to ``forward`` on its tangents."""
+        given = [a for a in (dA, db, dc) if a is not None]
+        if not given:
+            raise ValueError("forward_k needs at least one tangent")
+        k = int(given[0].shape[0])
+        B, n, m = self.batch, self.n, self.m
+        st = self._stage([dA, db, dc])
+        dev = st.mem == _lib.DOPT_MEM_DEVICE
+        kb = k * B
+        args = [colmajor(dA, (kb, m, n)) if dA is not None else None,
+                vector(db, (kb, m)) if db is not None else None,
+                vector(dc, (kb, n)) if dc is not None else None]
+        out = Staged.empty((k, B, self.N), dev)
+        dx = Staged.empty((k, B, n), dev)
+        rc = self.lib.dopt_conic_forward_k(self.h, k, *[st.ptr(a) for a in args], st.ptr(out), st.ptr(dx))
+        _lib.check(rc, self.h)
+        return out, dx
+
+    def lsqr_stats_k(self, k):
+        """(istop, iterations) per seed of the last ``reverse_k`` /
+        ``forward_k`` call with this k: dict of (k, B) arrays."""
+        k, B = int(k), self.batch
+        buf = np.zeros(2 * B * max(k, 1), dtype=np.int32)
+        _lib.check(self.lib.dopt_conic_lsqr_stats_k(self.h, k, buf.ctypes.data), self.h)
+        buf = buf.reshape(k, 2, B)
+        return {"istop": buf[:, 0, :], "iterations": buf[:, 1, :]}
+
     def set_maxiter(self, maxiter):
         """Cap LSQR at ``maxiter`` iterations (0: the reference's default
         max(size(M))) — dopt_conic_set_maxiter."""

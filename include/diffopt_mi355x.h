@@ -55,7 +55,7 @@ extern "C" {
 #define DOPT_CONE_SOC 3          /* MOI.SecondOrderCone                       */
 #define DOPT_CONE_PSD_TRI 4      /* MOI.PositiveSemidefiniteConeTriangle (side ≤ 4096; > 64 on global scratch) */
 
-#define DOPT_ABI_VERSION 2
+#define DOPT_ABI_VERSION 3
 
 typedef struct dopt_handle dopt_handle;
 
@@ -301,6 +301,31 @@ int dopt_conic_lsqr_stats(dopt_handle* h, int32_t* stats);
  * introspection (no reference counterpart: lsqr's log is not kept,
  * ConicProgram.jl:323, :372). */
 int dopt_conic_lsqr_norms(dopt_handle* h, double* norms);
+/* k seeds per solved cone program in one call: k reverse_differentiate!
+ * (ConicProgram.jl:336-394, getters :396-443) or k forward_differentiate!
+ * (:257-334) of every problem, where the reference re-runs lsqr(M, ·) once per
+ * seed (:323, :372).  Seed-major layout as dopt_qp_reverse_k: seed j's inputs
+ * and outputs are an ordinary batch block at offset j·B·len (dx n×B×k, out_g
+ * (n+m+1)×B×k, out_dA m×n×B×k col-major per problem, …).  The same pointers
+ * may be NULL as in dopt_conic_reverse / dopt_conic_forward; k >= 1 (else −1);
+ * factorises first if needed.  Seed j's outputs, istop and iteration count are
+ * bit-identical to the single-seed call on that seed alone, on every route —
+ * the per-seed special cases (a reverse seed with ‖dz‖ ≤ 1e-4 → 0, :369-370;
+ * a forward seed with an exactly zero RHS → 0, :320) and
+ * dopt_conic_set_maxiter included.  Dense persistent route (m ≤ 1024, PSD
+ * sides ≤ 64, not dopt_set_sparse): groups of up to 4 seeds co-iterate in one
+ * workgroup and share every sweep over A (k = 1: the single-seed kernel).
+ * Split route and sparse route: the single-seed LSQR once per seed inside the
+ * call — no shared sweep there yet.
+ * After a _k call dopt_conic_lsqr_stats, dopt_conic_lsqr_norms, dopt_get_info
+ * and dopt_get_system_size report seed 0. */
+int dopt_conic_reverse_k(dopt_handle* h, int32_t k, const double* dx, double* out_g,
+                         double* out_dA, double* out_db, double* out_dc);
+int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const double* db,
+                         const double* dc, double* out, double* out_dx);
+/* LSQR statistics of the last _k call, 2·B·k int32: per seed [istop (B) |
+ * iterations (B)].  −1 if the last conic call was not a _k call with this k. */
+int dopt_conic_lsqr_stats_k(dopt_handle* h, int32_t k, int32_t* stats);
 
 /* ---- introspection ---------------------------------------------------------*/
 /* per-problem status of the last factor/solve: QP: 0 ok, k>0 zero pivot at
