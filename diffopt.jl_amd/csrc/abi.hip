@@ -1266,6 +1266,10 @@ int dopt_qp_get_sym(dopt_handle* h, int8_t* flags) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_QP) throw Error(-1, "QP only");
     if (!flags) throw Error(-1, "flags is required");
+    if (h->sparse) {   // LSQR only: no factorisation, so no P-symmetric route (meta may be unallocated)
+      std::fill(flags, flags + h->batch, (int8_t)0);
+      return 0;
+    }
     std::vector<dopt::QPMeta> meta(h->batch);
     DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
                                   hipMemcpyDeviceToHost, h->stream));
@@ -1414,6 +1418,9 @@ int dopt_conic_set(dopt_handle* h, const double* A, const double* b, const doubl
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_set on a non-conic handle");
     if (h->sparse) throw Error(-1, "dopt_conic_set: a sparse-route handle takes the MOI matrix form (dopt_conic_set_csc)");
     if (!A) throw Error(-1, "A, b, c, x, s, y are required");
+    // the staging below overwrites the previous model's A before the cone
+    // table is validated: the handle holds no model until this call succeeds
+    h->cset = h->cfactored = false;
     conic_set_common(h, stage_in(*h, h->own_cin[0], A, (size_t)h->batch * h->m * h->n), b, c, x, s, y,
                      cone_desc, ncones);
     return 0;
@@ -1429,6 +1436,10 @@ int dopt_conic_set_csc(dopt_handle* h, const int64_t* A_colptr, const int64_t* A
     const size_t B = h->batch, n = h->n, m = h->m;
     if (!A_colptr) throw Error(-1, "A, b, c, x, s, y are required");
     if (A_nnz < 0 || (A_nnz > 0 && (!A_rowval || !A_nzval))) throw Error(-1, "bad CSC nnz / arrays");
+    // A is densified (or its sparse store rebuilt) before the CSC arrays and
+    // the cone table are validated: the handle holds no model until this
+    // call succeeds
+    h->cset = h->cfactored = false;
     h->csc_err.ensure(sizeof(int));
     DOPT_CHECK_HIP(hipMemsetAsync(h->csc_err.p, 0, sizeof(int), h->stream));
     const int64_t* cp = stage_in_i64(*h, h->csc_in[0], A_colptr, B * (n + 1));

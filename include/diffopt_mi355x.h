@@ -447,6 +447,8 @@ int dopt_qp_get_lu_kind(dopt_handle* h, int8_t* kinds);
 /* per-problem flag: 1 when the last factorisation took the P-symmetric
  * no-pivot route (P = diag(1, λ_k, 1) makes P·K symmetric: lower trailing
  * tiles only, U from L, ≈ N'³/3 flops instead of 2N'³/3), 0 otherwise.
+ * On a sparse-route handle (dopt_set_sparse) nothing is factorised: every
+ * flag is 0, whatever an earlier dense factorisation on the handle took.
  * Introspection for tests and the bench. */
 int dopt_qp_get_sym(dopt_handle* h, int8_t* flags);
 /* per-problem size of the factorised (reduced) KKT system (QP; NLP: n + c on

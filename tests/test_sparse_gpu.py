@@ -174,6 +174,12 @@ def test_sparse_route_refusals():
     assert list(e.iterative()) == [False]
     with pytest.raises(_lib.EngineError, match="sparse direct LU"):
         e.factor()
+    # dopt_qp_get_sym on the sparse route: nothing is factorised, so zeros (or a
+    # clear error), never a dense factorisation's flags
+    try:
+        np.testing.assert_array_equal(e.sym_route(), 0)
+    except _lib.EngineError:
+        pass
     # malformed CSC: the dense route's validation
     G = d["G"][0].copy()
     G.indices[0] = m + 5
