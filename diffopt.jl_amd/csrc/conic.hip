@@ -14,7 +14,8 @@
 //                  Dπᵀ w = J w, J w = tri(U (B ∘ (Uᵀ smat(w) U)) Uᵀ)
 //                  (Dπ = S²JS⁻² = Jᵀ: the convention pinned by the reference's
 //                  PSD fixtures, oracle/cones.py)
-#include "dopt_internal.h"
+#include "device_prims.h"
+#include "lsqr_core.h"
 
 #include <type_traits>
 
@@ -31,44 +32,6 @@ struct ConeDesc {
   int32_t woff, pad;             // PSD side > PSD_MAX: offset into the global scratch
 };
 
-
-// wave sum by DPP (VALU lane moves, no LDS crossbar): quad xor 1 / 2, the
-// half-row and row mirrors, then row_bcast:15 / 31 carry the rows' totals up;
-// the full sum lands in lane 63 (the other lanes hold partial sums)
-template <int CTRL, int ROWMASK, bool ZERO>
-__device__ __forceinline__ double cdpp(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp(ZERO ? 0 : (int)b, (int)b, CTRL, ROWMASK, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp(ZERO ? 0 : (int)(b >> 32), (int)(b >> 32), CTRL, ROWMASK, 0xF, false);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-__device__ __forceinline__ double wave_sum63(double v) {
-  v += cdpp<0xB1, 0xF, false>(v);    // quad_perm [1,0,3,2]
-  v += cdpp<0x4E, 0xF, false>(v);    // quad_perm [2,3,0,1]
-  v += cdpp<0x141, 0xF, false>(v);   // row_half_mirror
-  v += cdpp<0x140, 0xF, false>(v);   // row_mirror
-  v += cdpp<0x142, 0xA, true>(v);    // row_bcast:15 → rows 1, 3
-  v += cdpp<0x143, 0xC, true>(v);    // row_bcast:31 → rows 2, 3
-  return v;
-}
-
-// wave sum in every lane: the DPP sum, broadcast from lane 63
-__device__ __forceinline__ double cwave_sum(double v) {
-  v = wave_sum63(v);
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, 63);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
-
-__device__ __forceinline__ double cblock_sum(double v, double* red) {
-  v = cwave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  return red[0] + red[1] + red[2] + red[3];
-}
 
 __device__ __forceinline__ int psd_side(int dim) {
   int d = 0;
@@ -373,11 +336,6 @@ __device__ __forceinline__ void psd_apply_cone(const ConeDesc cd, const double* 
 // of B for the Hadamard product) is issued before the first use.  The middle
 // product UᵀXU is symmetric, so only its upper tiles are computed and mirrored;
 // the last one is stored as the upper triangle (MOI order) only.
-typedef double d4c __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ d4c cmfma(double a, double b, d4c c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 __device__ __forceinline__ void psd_apply_cone_lds(const ConeDesc cd, const double* __restrict__ P,
                                                    const double* in, double* out, int trans, double* Xs,
                                                    double* Ys, double* Us) {
@@ -863,6 +821,31 @@ __device__ __forceinline__ void MT_apply2(const ConicProblem& pr, const ConeDesc
 // problem (rhs2 / tol2 / xout2 / info2 / norms2, its own workspace) beside the
 // first — the forward and reverse runs of dopt_conic_forward_reverse.
 // ---------------------------------------------------------------------------
+// M (mul) and Mᵀ (tmul) of one problem as lsqr_solve's operator; s1, s2
+// (m each) and s4 (n): the applies' scratch
+template <class MAT>
+struct ConicM {
+  const ConicProblem& pr;
+  const MAT& mat;
+  const ConeDesc* cones;
+  int ncones;
+  double *s1, *s2, *s4, *lds, *red, *ys;
+  __device__ __forceinline__ void mul(const double* z, double* out) const {
+    M_apply(pr, mat, cones, ncones, z, out, s1, s2, s4, lds, red, ys);
+  }
+  __device__ __forceinline__ void tmul(const double* r, double* out) const {
+    MT_apply(pr, mat, cones, ncones, r, out, s1, s2, s4, lds, red, ys);
+  }
+};
+
+// norms[0..3] ← terminal rnorm, arnorm, xnorm, anorm
+__device__ __forceinline__ void lsqr_store_norms(double* norms, const LsqrScalars& st) {
+  norms[0] = st.rnorm;
+  norms[1] = st.arnorm;
+  norms[2] = st.xnorm;
+  norms[3] = st.anorm;
+}
+
 struct SpConic {
   const int64_t *cp, *rp;
   const int32_t *ri, *ci;
@@ -920,106 +903,16 @@ __global__ __launch_bounds__(CTPB) void conic_lsqr_kernel(
     mat = SparseA<SG>{sa.cp + (size_t)bidx * (n + 1), sa.rp + (size_t)bidx * (m + 1), sa.ri, sa.ci, sa.cv, sa.rv};
   else
     mat = DenseA{pr.A};
-  double bb = 0.0;
-  for (int i = t; i < N; i += CTPB) {
-    const double r = rb[i];
-    u[i] = r;
-    x[i] = 0.0;
-    bb = fma(r, r, bb);
-  }
-  double beta = sqrt(cblock_sum(bb, red));
-  int it = 0, istop = 0;
-  double fin[4] = {0.0, 0.0, 0.0, 0.0};   // terminal rnorm, arnorm, xnorm, anorm
-  if (beta > rhs_zero_tol) {
-    for (int i = t; i < N; i += CTPB) u[i] /= beta;
-    __syncthreads();
-    MT_apply(pr, mat, cn, ncones, u, vv, s1, s2, s4, lds, red, ys);
-    double aa = 0.0;
-    for (int i = t; i < N; i += CTPB) aa = fma(vv[i], vv[i], aa);
-    double alpha = sqrt(cblock_sum(aa, red));
-    if (alpha > 0.0) {
-      for (int i = t; i < N; i += CTPB) { vv[i] /= alpha; w[i] = vv[i]; }
-      __syncthreads();
-      const double eps = 2.220446049250313e-16;
-      const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
-      double anorm = 0.0, ddnorm = 0.0, res2 = 0.0, xxnorm = 0.0, zz = 0.0;
-      double sn2 = 0.0, cs2 = -1.0, rhobar = alpha, phibar = beta;
-      const double bnorm = beta;
-      while (it < maxiter) {
-        ++it;
-        M_apply(pr, mat, cn, ncones, vv, tmp, s1, s2, s4, lds, red, ys);
-        double su = 0.0;
-        for (int i = t; i < N; i += CTPB) { const double ui = tmp[i] - alpha * u[i]; u[i] = ui; su = fma(ui, ui, su); }
-        beta = sqrt(cblock_sum(su, red));
-        if (beta > 0.0) {
-          for (int i = t; i < N; i += CTPB) u[i] /= beta;
-          __syncthreads();
-          anorm = sqrt(anorm * anorm + alpha * alpha + beta * beta);
-          MT_apply(pr, mat, cn, ncones, u, tmp, s1, s2, s4, lds, red, ys);
-          double sv = 0.0;
-          for (int i = t; i < N; i += CTPB) { const double vi = tmp[i] - beta * vv[i]; vv[i] = vi; sv = fma(vi, vi, sv); }
-          alpha = sqrt(cblock_sum(sv, red));
-          if (alpha > 0.0) for (int i = t; i < N; i += CTPB) vv[i] /= alpha;
-          __syncthreads();
-        }
-        const double rhobar1 = rhobar;
-        const double rho = hypot(rhobar1, beta);
-        const double cs = rhobar1 / rho, sn = beta / rho;
-        const double theta = sn * alpha;
-        rhobar = -cs * alpha;
-        const double phi = cs * phibar;
-        phibar = sn * phibar;
-        const double tau = sn * phi;
-        const double t1 = phi / rho, t2 = -theta / rho;
-        double sw = 0.0;
-        for (int i = t; i < N; i += CTPB) {
-          const double wi = w[i];
-          sw = fma(wi, wi, sw);
-          x[i] = x[i] + t1 * wi;
-          w[i] = vv[i] + t2 * wi;
-        }
-        ddnorm += cblock_sum(sw, red) / (rho * rho);
-        const double delta = sn2 * rho, gambar = -cs2 * rho;
-        const double rhs_ = phi - delta * zz;
-        const double zbar = rhs_ / gambar;
-        const double xnorm = sqrt(xxnorm + zbar * zbar);
-        const double gamma = hypot(gambar, theta);
-        cs2 = gambar / gamma;
-        sn2 = theta / gamma;
-        zz = rhs_ / gamma;
-        xxnorm += zz * zz;
-        const double acond = anorm * sqrt(ddnorm);
-        const double rnorm = sqrt(phibar * phibar + res2);
-        const double arnorm = alpha * fabs(tau);
-        const double test1 = rnorm / bnorm;
-        const double test2 = (anorm * rnorm != 0.0) ? arnorm / (anorm * rnorm) : 0.0;
-        const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-        const double t1r = test1 / (1.0 + anorm * xnorm / bnorm);
-        const double rtol = btol + atol * anorm * xnorm / bnorm;
-        fin[0] = rnorm;
-        fin[1] = arnorm;
-        fin[2] = xnorm;
-        fin[3] = anorm;
-        istop = 0;
-        if (it >= maxiter) istop = 7;
-        if (1.0 + test3 <= 1.0) istop = 6;
-        if (1.0 + test2 <= 1.0) istop = 5;
-        if (1.0 + t1r <= 1.0) istop = 4;
-        if (test3 <= ctol) istop = 3;
-        if (test2 <= atol) istop = 2;
-        if (test1 <= rtol) istop = 1;
-        __syncthreads();
-        if (istop) break;
-      }
-    }
-  }
+  const ConicM<MAT> op{pr, mat, cn, ncones, s1, s2, s4, lds, red, ys};
+  LsqrScalars st;
+  lsqr_solve<CTPB, cblock_sum>(st, op, rb, rhs_zero_tol, maxiter, x, u, vv, w, tmp, N, red);
   __syncthreads();
   for (int i = t; i < N; i += CTPB) xout[(size_t)bidx * N + i] = x[i];
   if (t == 0 && info) {
-    info[bidx] = istop;
-    info[gridDim.x + bidx] = it;
+    info[bidx] = st.istop;
+    info[gridDim.x + bidx] = st.it;
   }
-  if (t < 4 && norms) norms[(size_t)4 * bidx + t] = fin[t];
+  if (t == 0 && norms) lsqr_store_norms(norms + (size_t)4 * bidx, st);
 }
 
 // ---------------------------------------------------------------------------
@@ -1031,12 +924,9 @@ __global__ __launch_bounds__(CTPB) void conic_lsqr_kernel(
 // stopped, the other continues on the single applies, so both results are
 // bit-identical to two conic_lsqr_kernel runs.
 // ---------------------------------------------------------------------------
-struct LsqrSeq {
+struct LsqrSeq : LsqrScalars {
   double *x, *u, *vv, *w, *tmp, *s1, *s2, *s4;
   const double* rb;
-  double alpha, beta, anorm, ddnorm, res2, xxnorm, zz, sn2, cs2, rhobar, phibar, bnorm;
-  double fin[4];   // terminal rnorm, arnorm, xnorm, anorm
-  int it, istop;
   bool live;
 };
 
@@ -1068,7 +958,7 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
   pr.m = m;
   pr.n = n;
   const size_t wl = (size_t)5 * N + 3 * (size_t)m + n;
-  LsqrSeq S[2];
+  LsqrSeq S[2] = {};
   for (int q = 0; q < 2; ++q) {
     LsqrSeq& Q = S[q];
     Q.x = work + ((size_t)2 * bidx + q) * wl;
@@ -1080,23 +970,11 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
     Q.s2 = Q.s1 + m;
     Q.s4 = Q.s2 + 2 * (size_t)m;
     Q.rb = (q == 0 ? rhs_f : rhs_r) + (size_t)bidx * N;
-    Q.it = 0;
-    Q.istop = 0;
-    Q.live = false;
-    Q.fin[0] = Q.fin[1] = Q.fin[2] = Q.fin[3] = 0.0;
-    double bb = 0.0;
-    for (int i = t; i < N; i += CTPB) {
-      const double r = Q.rb[i];
-      Q.u[i] = r;
-      Q.x[i] = 0.0;
-      bb = fma(r, r, bb);
-    }
-    Q.beta = sqrt(cblock_sum(bb, red));
+    Q.beta = sqrt(lsqr_load_rhs<CTPB, cblock_sum>(Q.rb, Q.u, Q.x, N, red));
   }
   const bool go0 = S[0].beta > tol_f, go1 = S[1].beta > tol_r;
   for (int q = 0; q < 2; ++q)
-    if (q == 0 ? go0 : go1)
-      for (int i = t; i < N; i += CTPB) S[q].u[i] /= S[q].beta;
+    if (q == 0 ? go0 : go1) lsqr_scale<CTPB>(S[q].u, N, S[q].beta);
   __syncthreads();
   if (go0 && go1)
     MT_apply2(pr, cn, ncones, S[0].u, S[0].vv, S[0].s1, S[0].s2, S[0].s4, S[1].u, S[1].vv, S[1].s1, S[1].s2,
@@ -1108,23 +986,14 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
   for (int q = 0; q < 2; ++q) {
     if (!(q == 0 ? go0 : go1)) continue;
     LsqrSeq& Q = S[q];
-    double aa = 0.0;
-    for (int i = t; i < N; i += CTPB) aa = fma(Q.vv[i], Q.vv[i], aa);
-    Q.alpha = sqrt(cblock_sum(aa, red));
+    Q.alpha = sqrt(lsqr_norm2<CTPB, cblock_sum>(Q.vv, N, red));
     if (Q.alpha > 0.0) {
-      for (int i = t; i < N; i += CTPB) { Q.vv[i] /= Q.alpha; Q.w[i] = Q.vv[i]; }
+      lsqr_scale_copy<CTPB>(Q.vv, Q.w, N, Q.alpha);
       __syncthreads();
-      Q.anorm = Q.ddnorm = Q.res2 = Q.xxnorm = Q.zz = 0.0;
-      Q.sn2 = 0.0;
-      Q.cs2 = -1.0;
-      Q.rhobar = Q.alpha;
-      Q.phibar = Q.beta;
-      Q.bnorm = Q.beta;
+      lsqr_begin(Q, Q.alpha, Q.beta);
       Q.live = true;
     }
   }
-  const double eps = 2.220446049250313e-16;
-  const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
   while (S[0].live || S[1].live) {
     // M·v of the live sequences
     if (S[0].live && S[1].live)
@@ -1139,13 +1008,11 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
       LsqrSeq& Q = S[q];
       if (!Q.live) continue;
       ++Q.it;
-      double su = 0.0;
-      for (int i = t; i < N; i += CTPB) { const double ui = Q.tmp[i] - Q.alpha * Q.u[i]; Q.u[i] = ui; su = fma(ui, ui, su); }
-      Q.beta = sqrt(cblock_sum(su, red));
+      Q.beta = sqrt(lsqr_bidiag<CTPB, cblock_sum>(Q.u, Q.tmp, Q.alpha, N, red));
       if (Q.beta > 0.0) {
-        for (int i = t; i < N; i += CTPB) Q.u[i] /= Q.beta;
+        lsqr_scale<CTPB>(Q.u, N, Q.beta);
         __syncthreads();
-        Q.anorm = sqrt(Q.anorm * Q.anorm + Q.alpha * Q.alpha + Q.beta * Q.beta);
+        lsqr_anorm(Q, Q.alpha, Q.beta);
         mt[q] = true;
       }
     }
@@ -1161,59 +1028,11 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
       LsqrSeq& Q = S[q];
       if (!Q.live) continue;
       if (mt[q]) {
-        double sv = 0.0;
-        for (int i = t; i < N; i += CTPB) { const double vi = Q.tmp[i] - Q.beta * Q.vv[i]; Q.vv[i] = vi; sv = fma(vi, vi, sv); }
-        Q.alpha = sqrt(cblock_sum(sv, red));
-        if (Q.alpha > 0.0) for (int i = t; i < N; i += CTPB) Q.vv[i] /= Q.alpha;
+        Q.alpha = sqrt(lsqr_bidiag<CTPB, cblock_sum>(Q.vv, Q.tmp, Q.beta, N, red));
+        if (Q.alpha > 0.0) lsqr_scale<CTPB>(Q.vv, N, Q.alpha);
         __syncthreads();
       }
-      const double rhobar1 = Q.rhobar;
-      const double rho = hypot(rhobar1, Q.beta);
-      const double cs = rhobar1 / rho, sn = Q.beta / rho;
-      const double theta = sn * Q.alpha;
-      Q.rhobar = -cs * Q.alpha;
-      const double phi = cs * Q.phibar;
-      Q.phibar = sn * Q.phibar;
-      const double tau = sn * phi;
-      const double t1 = phi / rho, t2 = -theta / rho;
-      double sw = 0.0;
-      for (int i = t; i < N; i += CTPB) {
-        const double wi = Q.w[i];
-        sw = fma(wi, wi, sw);
-        Q.x[i] = Q.x[i] + t1 * wi;
-        Q.w[i] = Q.vv[i] + t2 * wi;
-      }
-      Q.ddnorm += cblock_sum(sw, red) / (rho * rho);
-      const double delta = Q.sn2 * rho, gambar = -Q.cs2 * rho;
-      const double rhs_ = phi - delta * Q.zz;
-      const double zbar = rhs_ / gambar;
-      const double xnorm = sqrt(Q.xxnorm + zbar * zbar);
-      const double gamma = hypot(gambar, theta);
-      Q.cs2 = gambar / gamma;
-      Q.sn2 = theta / gamma;
-      Q.zz = rhs_ / gamma;
-      Q.xxnorm += Q.zz * Q.zz;
-      const double acond = Q.anorm * sqrt(Q.ddnorm);
-      const double rnorm = sqrt(Q.phibar * Q.phibar + Q.res2);
-      const double arnorm = Q.alpha * fabs(tau);
-      const double test1 = rnorm / Q.bnorm;
-      const double test2 = (Q.anorm * rnorm != 0.0) ? arnorm / (Q.anorm * rnorm) : 0.0;
-      const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-      const double t1r = test1 / (1.0 + Q.anorm * xnorm / Q.bnorm);
-      const double rtol = btol + atol * Q.anorm * xnorm / Q.bnorm;
-      Q.fin[0] = rnorm;
-      Q.fin[1] = arnorm;
-      Q.fin[2] = xnorm;
-      Q.fin[3] = Q.anorm;
-      int istop = 0;
-      if (Q.it >= maxiter) istop = 7;
-      if (1.0 + test3 <= 1.0) istop = 6;
-      if (1.0 + test2 <= 1.0) istop = 5;
-      if (1.0 + t1r <= 1.0) istop = 4;
-      if (test3 <= ctol) istop = 3;
-      if (test2 <= atol) istop = 2;
-      if (test1 <= rtol) istop = 1;
-      Q.istop = istop;
+      const int istop = lsqr_finish_step<CTPB, cblock_sum>(Q, Q.x, Q.w, Q.vv, N, maxiter, red);
       __syncthreads();
       if (istop) Q.live = false;
     }
@@ -1232,10 +1051,8 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
       info_r[bidx] = S[1].istop;
       info_r[gridDim.x + bidx] = S[1].it;
     }
-  }
-  if (t < 4) {
-    if (norms_f) norms_f[(size_t)4 * bidx + t] = S[0].fin[t];
-    if (norms_r) norms_r[(size_t)4 * bidx + t] = S[1].fin[t];
+    if (norms_f) lsqr_store_norms(norms_f + (size_t)4 * bidx, S[0]);
+    if (norms_r) lsqr_store_norms(norms_r + (size_t)4 * bidx, S[1]);
   }
 }
 
@@ -1260,18 +1077,16 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
 #endif
 constexpr int LSQRK_G = 4;   // widest group: ya + wr of gemv_multi<4> are 128 VGPRs, ys 64 KB of LDS
 
-struct SeqState {
-  double alpha, beta, anorm, ddnorm, res2, xxnorm, zz, sn2, cs2, rhobar, phibar, bnorm;
-  double fin0, fin1, fin2, fin3;   // terminal rnorm, arnorm, xnorm, anorm
-  int it, istop, live, mt;
+struct SeqState : LsqrScalars {
+  int live, mt;
 };
 // member-wise copies between LDS and registers (an aggregate copy keeps part of the struct on the stack)
 #define DOPT_SEQ_COPY(D, S_)                                                                              \
   do {                                                                                                    \
     (D).alpha = (S_).alpha; (D).beta = (S_).beta; (D).anorm = (S_).anorm; (D).ddnorm = (S_).ddnorm;       \
-    (D).res2 = (S_).res2; (D).xxnorm = (S_).xxnorm; (D).zz = (S_).zz; (D).sn2 = (S_).sn2;                 \
-    (D).cs2 = (S_).cs2; (D).rhobar = (S_).rhobar; (D).phibar = (S_).phibar; (D).bnorm = (S_).bnorm;       \
-    (D).fin0 = (S_).fin0; (D).fin1 = (S_).fin1; (D).fin2 = (S_).fin2; (D).fin3 = (S_).fin3;               \
+    (D).xxnorm = (S_).xxnorm; (D).zz = (S_).zz; (D).sn2 = (S_).sn2; (D).cs2 = (S_).cs2;                   \
+    (D).rhobar = (S_).rhobar; (D).phibar = (S_).phibar; (D).bnorm = (S_).bnorm;                           \
+    (D).rnorm = (S_).rnorm; (D).arnorm = (S_).arnorm; (D).xnorm = (S_).xnorm;                             \
     (D).it = (S_).it; (D).istop = (S_).istop; (D).live = (S_).live; (D).mt = (S_).mt;                     \
   } while (0)
 
@@ -1440,22 +1255,11 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
   for (int q = 0; q < ng; ++q) {
     const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
     const double* rb = rhs + ((size_t)(seed0 + q) * B + bidx) * N;
-    double bb = 0.0;
-    for (int i = t; i < N; i += CTPB) {
-      const double r = rb[i];
-      V.u[i] = r;
-      V.x[i] = 0.0;
-      bb = fma(r, r, bb);
-    }
-    const double beta = sqrt(cblock_sum(bb, red));
+    const double beta = sqrt(lsqr_load_rhs<CTPB, cblock_sum>(rb, V.u, V.x, N, red));
     const bool go = beta > rhs_zero_tol;
-    if (go)
-      for (int i = t; i < N; i += CTPB) V.u[i] /= beta;
+    if (go) lsqr_scale<CTPB>(V.u, N, beta);
     if (t == 0) {
-      SeqState Q;
-      Q.alpha = Q.anorm = Q.ddnorm = Q.res2 = Q.xxnorm = Q.zz = Q.sn2 = Q.cs2 = Q.rhobar = Q.phibar = Q.bnorm = 0.0;
-      Q.fin0 = Q.fin1 = Q.fin2 = Q.fin3 = 0.0;
-      Q.it = Q.istop = Q.mt = 0;
+      SeqState Q = {};
       Q.beta = beta;
       Q.live = go;   // until α is known: takes part in the first Mᵀ·u
       DOPT_SEQ_COPY(S[q], Q);
@@ -1468,25 +1272,16 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
     const SeqVec V = seq_vec(wb0 + (size_t)q * qs, N, m);
     SeqState Q;
     DOPT_SEQ_COPY(Q, S[q]);
-    double aa = 0.0;
-    for (int i = t; i < N; i += CTPB) aa = fma(V.vv[i], V.vv[i], aa);
-    Q.alpha = sqrt(cblock_sum(aa, red));
+    Q.alpha = sqrt(lsqr_norm2<CTPB, cblock_sum>(V.vv, N, red));
     Q.live = 0;
     if (Q.alpha > 0.0) {
-      for (int i = t; i < N; i += CTPB) { V.vv[i] /= Q.alpha; V.w[i] = V.vv[i]; }
+      lsqr_scale_copy<CTPB>(V.vv, V.w, N, Q.alpha);
       __syncthreads();
-      Q.anorm = Q.ddnorm = Q.res2 = Q.xxnorm = Q.zz = 0.0;
-      Q.sn2 = 0.0;
-      Q.cs2 = -1.0;
-      Q.rhobar = Q.alpha;
-      Q.phibar = Q.beta;
-      Q.bnorm = Q.beta;
+      lsqr_begin(Q, Q.alpha, Q.beta);
       Q.live = maxiter > 0;
     }
     if (t == 0) DOPT_SEQ_COPY(S[q], Q);
   }
-  const double eps = 2.220446049250313e-16;
-  const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
   while (true) {
     cnt = list_live<G>(S, ng, false, lstL, &lcnt);
     if (cnt == 0) break;
@@ -1499,13 +1294,11 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
       DOPT_SEQ_COPY(Q, S[q]);
       ++Q.it;
       Q.mt = 0;
-      double su = 0.0;
-      for (int i = t; i < N; i += CTPB) { const double ui = V.tmp[i] - Q.alpha * V.u[i]; V.u[i] = ui; su = fma(ui, ui, su); }
-      Q.beta = sqrt(cblock_sum(su, red));
+      Q.beta = sqrt(lsqr_bidiag<CTPB, cblock_sum>(V.u, V.tmp, Q.alpha, N, red));
       if (Q.beta > 0.0) {
-        for (int i = t; i < N; i += CTPB) V.u[i] /= Q.beta;
+        lsqr_scale<CTPB>(V.u, N, Q.beta);
         __syncthreads();
-        Q.anorm = sqrt(Q.anorm * Q.anorm + Q.alpha * Q.alpha + Q.beta * Q.beta);
+        lsqr_anorm(Q, Q.alpha, Q.beta);
         Q.mt = 1;
       }
       if (t == 0) DOPT_SEQ_COPY(S[q], Q);
@@ -1519,59 +1312,11 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
       SeqState Q;
       DOPT_SEQ_COPY(Q, S[q]);
       if (Q.mt) {
-        double sv = 0.0;
-        for (int i = t; i < N; i += CTPB) { const double vi = V.tmp[i] - Q.beta * V.vv[i]; V.vv[i] = vi; sv = fma(vi, vi, sv); }
-        Q.alpha = sqrt(cblock_sum(sv, red));
-        if (Q.alpha > 0.0) for (int i = t; i < N; i += CTPB) V.vv[i] /= Q.alpha;
+        Q.alpha = sqrt(lsqr_bidiag<CTPB, cblock_sum>(V.vv, V.tmp, Q.beta, N, red));
+        if (Q.alpha > 0.0) lsqr_scale<CTPB>(V.vv, N, Q.alpha);
         __syncthreads();
       }
-      const double rhobar1 = Q.rhobar;
-      const double rho = hypot(rhobar1, Q.beta);
-      const double cs = rhobar1 / rho, sn = Q.beta / rho;
-      const double theta = sn * Q.alpha;
-      Q.rhobar = -cs * Q.alpha;
-      const double phi = cs * Q.phibar;
-      Q.phibar = sn * Q.phibar;
-      const double tau = sn * phi;
-      const double t1 = phi / rho, t2 = -theta / rho;
-      double sw = 0.0;
-      for (int i = t; i < N; i += CTPB) {
-        const double wi = V.w[i];
-        sw = fma(wi, wi, sw);
-        V.x[i] = V.x[i] + t1 * wi;
-        V.w[i] = V.vv[i] + t2 * wi;
-      }
-      Q.ddnorm += cblock_sum(sw, red) / (rho * rho);
-      const double delta = Q.sn2 * rho, gambar = -Q.cs2 * rho;
-      const double rhs_ = phi - delta * Q.zz;
-      const double zbar = rhs_ / gambar;
-      const double xnorm = sqrt(Q.xxnorm + zbar * zbar);
-      const double gamma = hypot(gambar, theta);
-      Q.cs2 = gambar / gamma;
-      Q.sn2 = theta / gamma;
-      Q.zz = rhs_ / gamma;
-      Q.xxnorm += Q.zz * Q.zz;
-      const double acond = Q.anorm * sqrt(Q.ddnorm);
-      const double rnorm = sqrt(Q.phibar * Q.phibar + Q.res2);
-      const double arnorm = Q.alpha * fabs(tau);
-      const double test1 = rnorm / Q.bnorm;
-      const double test2 = (Q.anorm * rnorm != 0.0) ? arnorm / (Q.anorm * rnorm) : 0.0;
-      const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-      const double t1r = test1 / (1.0 + Q.anorm * xnorm / Q.bnorm);
-      const double rtol = btol + atol * Q.anorm * xnorm / Q.bnorm;
-      Q.fin0 = rnorm;
-      Q.fin1 = arnorm;
-      Q.fin2 = xnorm;
-      Q.fin3 = Q.anorm;
-      int istop = 0;
-      if (Q.it >= maxiter) istop = 7;
-      if (1.0 + test3 <= 1.0) istop = 6;
-      if (1.0 + test2 <= 1.0) istop = 5;
-      if (1.0 + t1r <= 1.0) istop = 4;
-      if (test3 <= ctol) istop = 3;
-      if (test2 <= atol) istop = 2;
-      if (test1 <= rtol) istop = 1;
-      Q.istop = istop;
+      const int istop = lsqr_finish_step<CTPB, cblock_sum>(Q, V.x, V.w, V.vv, N, maxiter, red);
       __syncthreads();
       if (istop) Q.live = 0;
       if (t == 0) DOPT_SEQ_COPY(S[q], Q);
@@ -1586,13 +1331,7 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
       info[((size_t)2 * (seed0 + q)) * B + bidx] = S[q].istop;
       info[((size_t)2 * (seed0 + q) + 1) * B + bidx] = S[q].it;
     }
-    if (seed0 + q == 0 && t == 0 && norms0) {
-      double* nb = norms0 + (size_t)4 * bidx;
-      nb[0] = S[0].fin0;
-      nb[1] = S[0].fin1;
-      nb[2] = S[0].fin2;
-      nb[3] = S[0].fin3;
-    }
+    if (seed0 + q == 0 && t == 0 && norms0) lsqr_store_norms(norms0 + (size_t)4 * bidx, S[0]);
   }
 }
 
@@ -1711,10 +1450,8 @@ constexpr int SPLIT_FUSE_NMAX = 4096;
 #endif
 constexpr int SPLIT_NC2 = DOPT_SPLIT_NC2;   // columns in flight per wave, two sequences (split passes)   // fused form: u_n / v'_n of a sequence in LDS
 
-struct LsqrState {
-  double alpha, beta, rhobar, phibar, anorm, ddnorm, xxnorm, zz, sn2, cs2, bnorm;
-  double rnorm, arnorm, xnorm;   // terminal estimates (with anorm)
-  int32_t it, istop, done, skipT;
+struct LsqrState : LsqrScalars {
+  int32_t done, skipT;
 };
 
 struct SplitWS {
@@ -1834,20 +1571,8 @@ __global__ __launch_bounds__(CTPB) void conic_split_dpi_kernel(
 // The per-problem vector kernels below run 1024-thread workgroups and issue
 // VU independent loads per thread before using them (vectors of N = 13 251
 // doubles at config 5 would otherwise serialise on load latency).
-constexpr int VT = 1024;
+constexpr int VT = 1024;   // 16 waves: vblock_sum
 constexpr int VU = 4;
-
-__device__ __forceinline__ double vblock_sum(double v, double* red) {
-  v = cwave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double s = 0.0;
-#pragma unroll
-  for (int k = 0; k < VT / 64; ++k) s += red[k];
-  return s;
-}
 
 // Σ_rb gpart[rb][j] (the row blocks' partial Aᵀ products) for j = threadIdx.x
 // + k·VT; four independent accumulators
@@ -1905,8 +1630,9 @@ __global__ __launch_bounds__(VT) void conic_split_upd_u_kernel(
     LsqrState* __restrict__ stv) {
   __shared__ double red[VT / 64];
   const int b = blockIdx.x, t = threadIdx.x;
-  LsqrState st = stv[b];
+  LsqrState& st = stv[b];   // read before the first block sum's barriers, written by thread 0 after the last
   if (st.done) return;
+  const double alpha = st.alpha;
   const int n = ws.n, m = ws.m, N = ws.N;
   const double* v = ws.vec(ws.v, b);
   double* out = ws.vec(ws.out, b);
@@ -1935,79 +1661,14 @@ __global__ __launch_bounds__(VT) void conic_split_upd_u_kernel(
   const double se = vblock_sum(-cu - bd, red);
   if (t == 0) out[N - 1] = se;
   __syncthreads();
-  const double beta = sqrt(axpy_norm2(u, out, st.alpha, N, red));
+  const double beta = sqrt(axpy_norm2(u, out, alpha, N, red));
   if (beta > 0.0) vscale(u, N, beta);
   if (t == 0) {
     st.it += 1;
     st.beta = beta;
     st.skipT = !(beta > 0.0);
-    if (beta > 0.0) st.anorm = sqrt(st.anorm * st.anorm + st.alpha * st.alpha + beta * beta);
-    stv[b] = st;
+    if (beta > 0.0) lsqr_anorm(st, alpha, beta);
   }
-}
-
-// One LSQR step's plane rotation (IterativeSolvers lsqr!, the loop body after
-// the bidiagonalisation) and, after the x / w update, its estimates and
-// stopping tests — shared by the split kernels so both forms compute the same
-// expressions.
-struct LsqrStep {
-  double rho, theta, rhobar, phi, phibar, tau, t1, t2;
-};
-__device__ __forceinline__ LsqrStep lsqr_rotate(const LsqrState& st, double alpha, double beta) {
-  LsqrStep g;
-  const double rhobar1 = st.rhobar;
-  g.rho = hypot(rhobar1, beta);
-  const double cs = rhobar1 / g.rho, sn = beta / g.rho;
-  g.theta = sn * alpha;
-  g.rhobar = -cs * alpha;
-  g.phi = cs * st.phibar;
-  g.phibar = sn * st.phibar;
-  g.tau = sn * g.phi;
-  g.t1 = g.phi / g.rho;
-  g.t2 = -g.theta / g.rho;
-  return g;
-}
-
-// updates st's recurrences and estimates; returns istop (0: go on)
-__device__ __forceinline__ int lsqr_tests(LsqrState& st, const LsqrStep& g, double alpha, double ddnorm,
-                                          int maxiter) {
-  const double eps = 2.220446049250313e-16;
-  const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
-  const double anorm = st.anorm, bnorm = st.bnorm;
-  const double delta = st.sn2 * g.rho, gambar = -st.cs2 * g.rho;
-  const double rhs_ = g.phi - delta * st.zz;
-  const double zbar = rhs_ / gambar;
-  const double xnorm = sqrt(st.xxnorm + zbar * zbar);
-  const double gamma = hypot(gambar, g.theta);
-  st.cs2 = gambar / gamma;
-  st.sn2 = g.theta / gamma;
-  st.zz = rhs_ / gamma;
-  st.xxnorm += st.zz * st.zz;
-  const double acond = anorm * sqrt(ddnorm);
-  const double rnorm = sqrt(g.phibar * g.phibar);
-  const double arnorm = alpha * fabs(g.tau);
-  const double test1 = rnorm / bnorm;
-  const double test2 = (anorm * rnorm != 0.0) ? arnorm / (anorm * rnorm) : 0.0;
-  const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-  const double t1r = test1 / (1.0 + anorm * xnorm / bnorm);
-  const double rtol = btol + atol * anorm * xnorm / bnorm;
-  int istop = 0;
-  if (st.it >= maxiter) istop = 7;
-  if (1.0 + test3 <= 1.0) istop = 6;
-  if (1.0 + test2 <= 1.0) istop = 5;
-  if (1.0 + t1r <= 1.0) istop = 4;
-  if (test3 <= ctol) istop = 3;
-  if (test2 <= atol) istop = 2;
-  if (test1 <= rtol) istop = 1;
-  st.alpha = alpha;
-  st.rhobar = g.rhobar;
-  st.phibar = g.phibar;
-  st.ddnorm = ddnorm;
-  st.istop = istop;
-  st.rnorm = rnorm;
-  st.arnorm = arnorm;
-  st.xnorm = xnorm;
-  return istop;
 }
 
 // finish Mᵀ·u into out: out_n = Σ_rb gpart − c·u_last, out_m += u_m,
@@ -2079,14 +1740,7 @@ __global__ __launch_bounds__(VT) void conic_split_init2_kernel(
     for (int r = t; r < nc; r += VT) pw[(size_t)b * PL + r] = r == 0 ? ww : 0.0;
   }
   if (t == 0) {
-    st.alpha = alpha;
-    st.anorm = st.ddnorm = st.xxnorm = st.zz = st.sn2 = 0.0;
-    st.cs2 = -1.0;
-    st.rhobar = alpha;
-    st.phibar = st.beta;
-    st.bnorm = st.beta;
-    st.it = 0;
-    st.istop = 0;
+    lsqr_begin(st, alpha, st.beta);
     if (!(alpha > 0.0)) split_finish(b, active, st);
     stv[b] = st;
   }
@@ -2340,7 +1994,7 @@ __global__ __launch_bounds__(64 * NW) void conic_fsplit_pass_kernel(
         st.it += 1;
         st.beta = beta;
         st.skipT = !(beta > 0.0);
-        if (beta > 0.0) st.anorm = sqrt(st.anorm * st.anorm + al[ci] * al[ci] + beta * beta);
+        if (beta > 0.0) lsqr_anorm(st, al[ci], beta);
       }
       const double dv = beta > 0.0 ? beta : 1.0;   // β = 0: u stays u' (skipT), as upd_u
       for (int j = t; j < n; j += TPB) {
@@ -2617,8 +2271,6 @@ __global__ __launch_bounds__(CTPB) void conic_fsplit_dpiV_kernel(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static void ccheck() { DOPT_CHECK_HIP(hipGetLastError()); }
-
 // dynamic LDS of the Dπ apply: three dp × (dp+1) images of the largest PSD
 // cone up to PSD_MAX (larger ones use global scratch) — sized to the cones
 // present, so small-PSD batches keep two or more workgroups per CU
@@ -2676,7 +2328,7 @@ void conic_factor(Handle& h) {
                          h.cone_dev.as<ConeDesc>(), nc, h.cy, h.cs, m, h.dpi_len,
                          h.vp.as<double>(), h.vp.as<double>() + (size_t)B * m, h.dpi.as<double>(), bad,
                          h.psd_eig.as<double>(), h.psd_big_len);
-      ccheck();
+      check_launch();
     }
   }
   int hbad = 0;
@@ -2841,7 +2493,7 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
     hipLaunchKernelGGL(conic_split_init2_kernel, dim3(S.V), dim3(VT), 0, S.st, S.bv, S.cv, S.ws, S.stv, S.active,
                        fuse ? S.fs.part + 3 * RB + nc : nullptr, PL, nc);
   }
-  ccheck();
+  check_launch();
   if (fuse) {
     const size_t dlv = ((dl + 15) & ~(size_t)15) + (size_t)n * sizeof(double);
     const int img = (int)(((dl + 15) & ~(size_t)15) / sizeof(double));
@@ -2884,7 +2536,7 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
           }
       it += k;
       chunk = std::min(2 * chunk, SPLIT_CHUNK_MAX);
-      ccheck();
+      check_launch();
       for (int s = 0; s < ns; ++s)
         if (sl[s].left > 0)
           DOPT_CHECK_HIP(hipMemcpyAsync(&sl[s].left, sl[s].active, sizeof(int32_t), hipMemcpyDeviceToHost, sl[s].st));
@@ -2903,7 +2555,7 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
         hipLaunchKernelGGL(conic_split_upd_v_kernel, dim3(S.V), dim3(VT), 0, S.st, S.bv, S.cv, S.ws, S.stv, maxit,
                            S.active);
       }
-      ccheck();
+      check_launch();
       DOPT_CHECK_HIP(hipMemcpyAsync(&S.left, S.active, sizeof(int32_t), hipMemcpyDeviceToHost, S.st));
       DOPT_CHECK_HIP(hipStreamSynchronize(S.st));
     }
@@ -2920,7 +2572,7 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
     DOPT_CHECK_HIP(hipEventRecord(h.ev_join, h.aux));
     DOPT_CHECK_HIP(hipStreamWaitEvent(h.stream, h.ev_join, 0));
   }
-  ccheck();
+  check_launch();
 }
 
 static bool use_split(const Handle& h) {
@@ -2956,7 +2608,7 @@ static void conic_lsqr_sparse(Handle& h, int nq, double tol, const double* rhs, 
   if (G == 1) go(conic_lsqr_kernel<true, 1>);
   else if (G == 4) go(conic_lsqr_kernel<true, 4>);
   else go(conic_lsqr_kernel<true, 16>);
-  ccheck();
+  check_launch();
 }
 
 static void conic_lsqr(Handle& h, double tol, double* out) {
@@ -2983,7 +2635,7 @@ static void conic_lsqr(Handle& h, double tol, double* out) {
                      h.dpi.as<double>(), h.dpi_len, m, n, rhs, tol, h.cwork.as<double>(), out,
                      h.cinfo.as<int32_t>(), h.cnorm.as<double>(), lsqr_maxiter(h), SpConic{}, nullptr, 0.0, nullptr,
                      nullptr, nullptr);
-  ccheck();
+  check_launch();
 }
 
 void conic_forward(Handle& h, const double* dA, const double* db, const double* dc,
@@ -2998,13 +2650,13 @@ void conic_forward(Handle& h, const double* dA, const double* db, const double* 
     PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
     hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA, db, dc, h.cx,
                        h.vp.as<double>() + (size_t)B * m, m, n, rhs);
-    ccheck();
+    check_launch();
   }
   conic_lsqr(h, 0.0, out);   // `norm(RHS) <= 1e-400` ≡ RHS == 0 (ConicProgram.jl:320)
   if (out_dx) {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
     hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out, h.cx, m, n, out_dx);
-    ccheck();
+    check_launch();
   }
 }
 
@@ -3019,14 +2671,14 @@ void conic_reverse(Handle& h, const double* dx, double* out_g, double* out_dA, d
   {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
     hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx, h.cx, m, n, rhs);
-    ccheck();
+    check_launch();
   }
   conic_lsqr(h, 1e-4, out_g);  // `norm(dz) <= 1e-4` → g = 0 (ConicProgram.jl:369-370)
   if (out_dA || out_db || out_dc) {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
     hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g, h.cx,
                        h.vp.as<double>() + (size_t)B * m, m, n, out_dA, out_db, out_dc);
-    ccheck();
+    check_launch();
   }
 }
 
@@ -3056,7 +2708,7 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
     hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA, db, dc, h.cx,
                        h.vp.as<double>() + (size_t)B * m, m, n, rhs_f);
     hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx, h.cx, m, n, rhs_r);
-    ccheck();
+    check_launch();
   }
   if (h.sparse) {   // the two sequences side by side in one launch (each equal to its separate call)
     int32_t* info = h.cinfo.as<int32_t>();
@@ -3071,7 +2723,7 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
                        h.cone_dev.as<ConeDesc>(), nc, h.cA, h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(),
                        h.dpi_len, m, n, rhs_f, 0.0, rhs_r, 1e-4, h.cwork.as<double>(), out_f, out_g,
                        info + 2 * B, info, nrm + 4 * (size_t)B, nrm, lsqr_maxiter(h));
-    ccheck();
+    check_launch();
   }
   PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
   if (out_dx)
@@ -3079,7 +2731,7 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
   if (out_dA || out_db || out_dc)
     hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g, h.cx,
                        h.vp.as<double>() + (size_t)B * m, m, n, out_dA, out_db, out_dc);
-  ccheck();
+  check_launch();
 }
 
 // ---------------------------------------------------------------------------
@@ -3120,7 +2772,7 @@ static void conic_lsqr_k(Handle& h, int k, double tol, const double* rhs, double
   };
   if (fits(LSQRK_G)) go(conic_lsqrk_kernel<LSQRK_G>, LSQRK_G);
   else go(conic_lsqrk_kernel<2>, 2);   // PSD sides near PSD_MAX: their Dπ images leave LDS for two sequences' ys
-  ccheck();
+  check_launch();
   // seed 0's [istop | iterations] where a single call leaves them (its norms: written there by the kernel)
   DOPT_CHECK_HIP(hipMemcpyAsync(h.cinfo.p, h.cinfok.p, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToDevice,
                                 h.stream));
@@ -3149,7 +2801,7 @@ void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* 
     for (int j = 0; j < k; ++j)
       hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx + j * Bz * n, h.cx, m, n,
                          rhs + j * Bz * N);
-    ccheck();
+    check_launch();
   }
   conic_lsqr_k(h, k, 1e-4, rhs, out_g);   // per seed: `norm(dz) <= 1e-4` → g = 0 (ConicProgram.jl:369-370)
   if (out_dA || out_db || out_dc) {
@@ -3158,7 +2810,7 @@ void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* 
       hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g + j * Bz * N, h.cx,
                          h.vp.as<double>() + Bz * m, m, n, out_dA ? out_dA + j * Bz * m * n : nullptr,
                          out_db ? out_db + j * Bz * m : nullptr, out_dc ? out_dc + j * Bz * n : nullptr);
-    ccheck();
+    check_launch();
   }
 }
 
@@ -3186,7 +2838,7 @@ void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const
       hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA ? dA + j * Bz * m * n : nullptr,
                          db ? db + j * Bz * m : nullptr, dc ? dc + j * Bz * n : nullptr, h.cx,
                          h.vp.as<double>() + Bz * m, m, n, rhs + j * Bz * N);
-    ccheck();
+    check_launch();
   }
   conic_lsqr_k(h, k, 0.0, rhs, out);   // per seed: RHS == 0 → 0 (ConicProgram.jl:320)
   if (out_dx) {
@@ -3194,7 +2846,7 @@ void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const
     for (int j = 0; j < k; ++j)
       hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out + j * Bz * N, h.cx, m, n,
                          out_dx + j * Bz * n);
-    ccheck();
+    check_launch();
   }
 }
 

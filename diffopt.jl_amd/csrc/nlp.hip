@@ -27,6 +27,7 @@
 // one value per element computed by gather — no zero-then-scatter pass.
 // Inertia correction adds k·st·D, D = +1 except −1 on the constraint rows.
 #include "nlp_defs.h"
+#include "qp_assemble.h"
 
 #include <algorithm>
 
@@ -948,8 +949,6 @@ std::vector<int32_t> singular_list(Handle& h, const std::vector<int32_t>& among)
 }  // namespace
 
 NLPDims nlp_dims(const Handle& h) { return dims(h); }
-__global__ void qp_qsym_kernel(QPIn, double*, int32_t*, const int32_t*);
-int qsym_pairs(int n);
 NLPMap nlp_map_of(const Handle& h) { return map_of(h); }
 NLPIn nlp_inputs(const Handle& h) { return inputs(h); }
 NLPRed nlp_red_of(Handle& h) { return red_of(h); }

@@ -15,32 +15,15 @@
 //   s     : m doubles  (G z − h, Julia sparse-matvec summation order)
 //   kidx  : m int32 (kept inequality rows, ascending)  rpos: m int32 (row → kk | -1)
 //   meta  : QPMeta {nk, nsys, iterative, info, lu}
-#include "dopt_internal.h"
+#include "device_prims.h"
+#include "lsqr_core.h"
+#include "qp_assemble.h"
 
 namespace dopt {
-
-typedef double d4 __attribute__((ext_vector_type(4)));
 
 constexpr int TPB = 256;   // threads per workgroup (4 waves)
 constexpr int OUT_LCAP = 4096;   // reverse outputs: eliminated rows listed in LDS up to this m
 constexpr int NB = 32;     // LU panel width
-
-__device__ __forceinline__ double wave_sum(double v) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  return v;
-}
-
-// block-wide sum; `red` = LDS scratch of >= 4 doubles; all threads get result
-__device__ __forceinline__ double block_sum(double v, double* red) {
-  v = wave_sum(v);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double r = red[0] + red[1] + red[2] + red[3];
-  return r;
-}
 
 // ---------------------------------------------------------------------------
 // 3. generic LU (reduced systems larger than BLOCKED_MAX, and blocked ones
@@ -271,6 +254,14 @@ __device__ __forceinline__ void dense_matvec(const double* __restrict__ Kb, int 
   __syncthreads();
 }
 
+// LHS (trans = 0) or LHSᵀ as lsqr_solve's operator
+struct DenseKKT {
+  const double* Kb;
+  int ld, N, trans;
+  __device__ __forceinline__ void mul(const double* v, double* out) const { dense_matvec(Kb, ld, N, trans, v, out); }
+  __device__ __forceinline__ void tmul(const double* u, double* out) const { dense_matvec(Kb, ld, N, !trans, u, out); }
+};
+
 __global__ __launch_bounds__(TPB) void qp_lsqr_kernel(
     const double* __restrict__ K, const QPMeta* __restrict__ meta, int nmax,
     int ld, int trans, const double* __restrict__ rhs, double* __restrict__ xout,
@@ -285,95 +276,9 @@ __global__ __launch_bounds__(TPB) void qp_lsqr_kernel(
   double* v = u + N;
   double* w = v + N;
   double* tmp = w + N;
-  double bb = 0.0;
-  for (int i = t; i < N; i += TPB) {
-    const double r = rhs[(size_t)b * nmax + i];
-    u[i] = r;
-    x[i] = 0.0;
-    bb = fma(r, r, bb);
-  }
-  double beta = sqrt(block_sum(bb, red));
-  int it = 0;
-  if (beta > 0.0) {
-    for (int i = t; i < N; i += TPB) u[i] /= beta;
-    __syncthreads();
-    dense_matvec(Kb, ld, N, !trans, u, v);   // v = Aᵀu
-    double aa = 0.0;
-    for (int i = t; i < N; i += TPB) aa = fma(v[i], v[i], aa);
-    double alpha = sqrt(block_sum(aa, red));
-    if (alpha > 0.0) {
-      for (int i = t; i < N; i += TPB) { v[i] /= alpha; w[i] = v[i]; }
-      __syncthreads();
-      const double eps = 2.220446049250313e-16;
-      const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
-      double anorm = 0.0, ddnorm = 0.0, res2 = 0.0, xxnorm = 0.0, zz = 0.0;
-      double sn2 = 0.0, cs2 = -1.0, rhobar = alpha, phibar = beta;
-      const double bnorm = beta;
-      const int maxiter = N;
-      while (it < maxiter) {
-        ++it;
-        dense_matvec(Kb, ld, N, trans, v, tmp);   // tmp = A v
-        double su = 0.0;
-        for (int i = t; i < N; i += TPB) { const double ui = tmp[i] - alpha * u[i]; u[i] = ui; su = fma(ui, ui, su); }
-        beta = sqrt(block_sum(su, red));
-        if (beta > 0.0) {
-          for (int i = t; i < N; i += TPB) u[i] /= beta;
-          __syncthreads();
-          anorm = sqrt(anorm * anorm + alpha * alpha + beta * beta);
-          dense_matvec(Kb, ld, N, !trans, u, tmp);  // tmp = Aᵀu
-          double sv = 0.0;
-          for (int i = t; i < N; i += TPB) { const double vi = tmp[i] - beta * v[i]; v[i] = vi; sv = fma(vi, vi, sv); }
-          alpha = sqrt(block_sum(sv, red));
-          if (alpha > 0.0) for (int i = t; i < N; i += TPB) v[i] /= alpha;
-          __syncthreads();
-        }
-        const double rhobar1 = rhobar;
-        const double rho = hypot(rhobar1, beta);
-        const double cs = rhobar1 / rho, sn = beta / rho;
-        const double theta = sn * alpha;
-        rhobar = -cs * alpha;
-        const double phi = cs * phibar;
-        phibar = sn * phibar;
-        const double tau = sn * phi;
-        const double t1 = phi / rho, t2 = -theta / rho;
-        double sw = 0.0;
-        for (int i = t; i < N; i += TPB) {
-          const double wi = w[i];
-          sw = fma(wi, wi, sw);
-          x[i] = x[i] + t1 * wi;
-          w[i] = v[i] + t2 * wi;
-        }
-        ddnorm += block_sum(sw, red) / (rho * rho);
-        const double delta = sn2 * rho, gambar = -cs2 * rho;
-        const double rhs_ = phi - delta * zz;
-        const double zbar = rhs_ / gambar;
-        const double xnorm = sqrt(xxnorm + zbar * zbar);
-        const double gamma = hypot(gambar, theta);
-        cs2 = gambar / gamma;
-        sn2 = theta / gamma;
-        zz = rhs_ / gamma;
-        xxnorm += zz * zz;
-        const double acond = anorm * sqrt(ddnorm);
-        const double rnorm = sqrt(phibar * phibar + res2);
-        const double arnorm = alpha * fabs(tau);
-        const double test1 = rnorm / bnorm;
-        const double test2 = (anorm * rnorm != 0.0) ? arnorm / (anorm * rnorm) : 0.0;
-        const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-        const double t1r = test1 / (1.0 + anorm * xnorm / bnorm);
-        const double rtol = btol + atol * anorm * xnorm / bnorm;
-        int istop = 0;
-        if (it >= maxiter) istop = 7;
-        if (1.0 + test3 <= 1.0) istop = 6;
-        if (1.0 + test2 <= 1.0) istop = 5;
-        if (1.0 + t1r <= 1.0) istop = 4;
-        if (test3 <= ctol) istop = 3;
-        if (test2 <= atol) istop = 2;
-        if (test1 <= rtol) istop = 1;
-        __syncthreads();
-        if (istop) break;
-      }
-    }
-  }
+  const DenseKKT op{Kb, ld, N, trans};
+  LsqrScalars st;
+  lsqr_solve<TPB, block_sum>(st, op, rhs + (size_t)b * nmax, 0.0, N, x, u, v, w, tmp, N, red);
   __syncthreads();
   for (int i = t; i < N; i += TPB) xout[(size_t)b * nmax + i] = x[i];
 }
@@ -745,20 +650,6 @@ void csc_to_dense3(Handle& h, const CscTriple& T) {
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-static void check_launch() { DOPT_CHECK_HIP(hipGetLastError()); }
-
-// qp_assemble.hip
-template <int RPT>
-__global__ void qp_prep_kernel(QPIn, double*, int32_t*, int32_t*, double*, double*, int64_t, QPMeta*,
-                               const int32_t*, double*, int);
-__global__ void qp_asm_tile_kernel(QPIn, const int32_t*, const double*, const double*, int64_t, QPMeta*, double*,
-                                   int, int, const int32_t*, int, double*);
-__global__ void qp_qsym_kernel(QPIn, double*, int32_t*, const int32_t*);
-int qsym_pairs(int n);
-int prep_rows_per_thread(int m);
-int prep_threads(int m);
-size_t prep_lds(int n);
-
 constexpr int ZCAP = 4096;   // z staged in LDS by the RHS / output kernels up to this n
 
 static double* dinv_of(Handle& h) {

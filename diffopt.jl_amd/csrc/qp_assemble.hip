@@ -42,7 +42,7 @@
 //
 // Reference: QuadraticProgram.jl create_LHS_matrix :256-282, `iterative`
 // :333/:436; the elimination is exact algebra.
-#include "dopt_internal.h"
+#include "qp_assemble.h"
 
 namespace dopt {
 

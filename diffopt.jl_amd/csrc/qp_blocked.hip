@@ -23,13 +23,11 @@
 //
 // Reference: QuadraticProgram.jl create_LHS_matrix :256-282 and the `LHS \ RHS`
 // of solve_system :486-496 (reverse :316-351, forward :357-446).
-#include "dopt_internal.h"
+#include "device_prims.h"
 
 namespace dopt {
 
 namespace {
-
-typedef double d4b __attribute__((ext_vector_type(4)));
 
 constexpr int BNB = 32;                  // panel width
 constexpr int BLP = BNB + 1;             // padded LDS row of a 32×32 block
@@ -39,19 +37,8 @@ constexpr int BDINV = 2 * BNB * BNB;     // doubles per panel in dinv (L11⁻¹ 
 #endif
 constexpr int PT = DOPT_SOLVE_PT;        // solve workgroup size (tuning builds: -DDOPT_SOLVE_PT)
 
-__device__ __forceinline__ d4b bmfma(double a, double b, d4b c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
-
 // wave max of a double (DPP butterfly within rows, row_bcast across rows,
 // result broadcast from lane 63)
-template <int CTRL, int ROWMASK>
-__device__ __forceinline__ double dpp_f64(double v) {
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_update_dpp((int)b, (int)b, CTRL, ROWMASK, 0xF, false);
-  const int hi = __builtin_amdgcn_update_dpp((int)(b >> 32), (int)(b >> 32), CTRL, ROWMASK, 0xF, false);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
-}
 __device__ __forceinline__ double wave_max_f64(double v) {
   v = fmax(v, dpp_f64<0xB1, 0xF>(v));    // quad_perm [1,0,3,2]
   v = fmax(v, dpp_f64<0x4E, 0xF>(v));    // quad_perm [2,3,0,1]
@@ -59,10 +46,7 @@ __device__ __forceinline__ double wave_max_f64(double v) {
   v = fmax(v, dpp_f64<0x140, 0xF>(v));   // row_mirror
   v = fmax(v, dpp_f64<0x142, 0xA>(v));   // row_bcast:15
   v = fmax(v, dpp_f64<0x143, 0xC>(v));   // row_bcast:31
-  const long long b = __double_as_longlong(v);
-  const int lo = __builtin_amdgcn_readlane((int)b, 63);
-  const int hi = __builtin_amdgcn_readlane((int)(b >> 32), 63);
-  return __longlong_as_double((long long)(((unsigned long long)(unsigned)hi << 32) | (unsigned)lo));
+  return readlane_d(v, 63);
 }
 // sum over each group of 8 lanes, in every lane of the group, by DPP (quad
 // xor 1, xor 2, then the half-row mirror: lane i + lane 7 − i): the same
@@ -333,11 +317,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2))) void b
       double up[BNB / 4];
 #pragma unroll
       for (int s = 0; s < BNB / 4; ++s) up[s] = Kb[rp[s] + colL];
-      d4b c0v = {bv[0], bv[1], bv[2], bv[3]}, c1v = {bv[4], bv[5], bv[6], bv[7]};
+      d4 c0v = {bv[0], bv[1], bv[2], bv[3]}, c1v = {bv[4], bv[5], bv[6], bv[7]};
 #pragma unroll
       for (int s = 0; s < BNB / 4; ++s) {
-        c0v = bmfma(lp0[s], up[s], c0v);
-        c1v = bmfma(lp1[s], up[s], c1v);
+        c0v = mfma_f64(lp0[s], up[s], c0v);
+        c1v = mfma_f64(lp1[s], up[s], c1v);
       }
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
@@ -345,11 +329,11 @@ __global__ __launch_bounds__(TPB) __attribute__((amdgpu_waves_per_eu(2))) void b
         bv[4 + rr] = c1v[rr];
       }
     }
-    d4b u0 = {0, 0, 0, 0}, u1 = {0, 0, 0, 0};
+    d4 u0 = {0, 0, 0, 0}, u1 = {0, 0, 0, 0};
 #pragma unroll
     for (int s = 0; s < BNB / 4; ++s) {
-      u0 = bmfma(a0[s], bv[s], u0);
-      u1 = bmfma(a1[s], bv[s], u1);
+      u0 = mfma_f64(a0[s], bv[s], u0);
+      u1 = mfma_f64(a1[s], bv[s], u1);
     }
     const int qn = q + TW;
     if (qn < ntile) {   // prefetch the next strip before storing this one
@@ -418,7 +402,7 @@ __global__ __launch_bounds__(256) void blu_update_kernel(double* __restrict__ K,
   const bool wact = rt * 64 + 16 * wv < R2;   // wave-uniform
   const int nq = min(4, (C2 - ct * 64) >> 4);
   double a[KW / 4];
-  d4b acc[4];
+  d4 acc[4];
   size_t ro[4];
   if (wact) {
     const double* arow = Kb + (size_t)pb[rbase + l16] * ld + c0;
@@ -441,7 +425,7 @@ __global__ __launch_bounds__(256) void blu_update_kernel(double* __restrict__ K,
 #pragma unroll
     for (int q = 0; q < 4; ++q) bq[q] = U[(4 * s + g) * ULD + 16 * q + l16];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = bmfma(a[s], bq[q], acc[q]);
+    for (int q = 0; q < 4; ++q) acc[q] = mfma_f64(a[s], bq[q], acc[q]);
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {

@@ -21,22 +21,16 @@
 //   trans 0:  K x = b   →  L U x = P b
 //   trans 1:  Kᵀ x = b  →  Uᵀ w = b, Lᵀ v = w, x = Pᵀ v
 // Right-hand sides and solutions: seed j of problem b at rhs + (j·B + b)·nmax.
-#include "dopt_internal.h"
+#include "device_prims.h"
 
 namespace dopt {
 
 namespace {
 
-typedef double d4m __attribute__((ext_vector_type(4)));
-
 constexpr int MBN = 32;                  // factor block width (the solves' 32-blocks)
 constexpr int MDB = 2 * MBN * MBN;       // doubles per 32-block in dinv (L⁻¹ | U⁻¹)
 constexpr int MKC = 16;                  // right-hand sides per workgroup
 constexpr int MT = 256;                  // threads per workgroup
-
-__device__ __forceinline__ d4m mmfma(double a, double b, d4m c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ int multi_np(const QPMeta& mm) {
   if (qp_route(mm.iterative, mm.nsys) != ROUTE_BLOCKED) return 0;
@@ -82,7 +76,7 @@ __global__ __launch_bounds__(MT) void blu_solve_multi_kernel(const double* __res
       const int bk = fwd ? s : nblk - 1 - s;
       const int i0 = bk * MBN;
       // ---- X = D · V_k (D = the block's L⁻¹ / U⁻¹, transposed for Kᵀ)
-      d4m xa = {0, 0, 0, 0};
+      d4 xa = {0, 0, 0, 0};
       if (wv < 2) {
         const double* Dk = Db + (size_t)bk * MDB + (useU ? MBN * MBN : 0);
         const int r = 16 * wv + l16;
@@ -94,7 +88,7 @@ __global__ __launch_bounds__(MT) void blu_solve_multi_kernel(const double* __res
           vv[q] = V[(i0 + j) * MKC + l16];
         }
 #pragma unroll
-        for (int q = 0; q < 8; ++q) xa = mmfma(dv[q], vv[q], xa);
+        for (int q = 0; q < 8; ++q) xa = mfma_f64(dv[q], vv[q], xa);
       }
       __syncthreads();   // every read of V_k is done
       if (wv < 2) {
@@ -117,11 +111,11 @@ __global__ __launch_bounds__(MT) void blu_solve_multi_kernel(const double* __res
           const int j = i0 + 8 * g + q;   // trans 0: 64 contiguous bytes of row e per lane
           av[q] = TRANS ? Kb[(size_t)ps[j] * ld + e] : Kb[(size_t)ps[e] * ld + j];
         }
-        d4m acc;
+        d4 acc;
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) acc[rr] = V[(r0 + g + 4 * rr) * MKC + l16];
 #pragma unroll
-        for (int q = 0; q < 8; ++q) acc = mmfma(-av[q], xb[q], acc);
+        for (int q = 0; q < 8; ++q) acc = mfma_f64(-av[q], xb[q], acc);
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) V[(r0 + g + 4 * rr) * MKC + l16] = acc[rr];
       }

@@ -61,6 +61,7 @@
 //
 // Reference: QuadraticProgram.jl create_LHS_matrix :256-282 and solve_system
 // :486-496 (reverse :316-351, forward :357-446).
+#include "device_prims.h"
 #include "nlp_defs.h"
 
 // tools/probe/nlu_probe.hip builds this file with -DNLU_STOP=k to time the
@@ -104,8 +105,6 @@ namespace dopt {
 
 namespace {
 
-typedef double d4n __attribute__((ext_vector_type(4)));
-
 constexpr int NB64 = 64;           // diagonal block width
 constexpr int SLD = NB64 + 1;      // LDS row stride of the 64√ó64 block
 constexpr int PNT = 256;           // panel threads
@@ -114,10 +113,6 @@ constexpr int DBLK = 2 * 32 * 32;  // doubles per 32-block in dinv (L‚Åª¬π | U‚Å
 // then (P-symmetric problems) its 64 ratios u_kk / p_k
 constexpr int BUKP = NB64 * NB64;
 constexpr int BSTR = NB64 * NB64 + NB64;
-
-__device__ __forceinline__ d4n nmfma(double a, double b, d4n c) {
-  return __builtin_amdgcn_mfma_f64_16x16x4f64(a, b, c, 0, 0, 0);
-}
 
 __device__ __forceinline__ int nlu_np(const QPMeta& mm) {
   if (qp_route(mm.iterative, mm.nsys) != ROUTE_BLOCKED) return 0;
@@ -281,27 +276,6 @@ __device__ __forceinline__ void col_lower_tile(int tile, int nrt, int& rt, int& 
 // into S, the U part is written from the registers at the end.  Returns the
 // wave's threshold verdict (1: a zero / non-finite pivot or |l| > NOPIV_LMAX).
 // ---------------------------------------------------------------------------
-__device__ __forceinline__ void wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-
-// 1/d: v_rcp_f64 + two Newton steps
-__device__ __forceinline__ double rcp_nr(double d) {
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(fma(-d, r, 1.0), r, r);
-  return fma(fma(-d, r, 1.0), r, r);
-}
-
-// lane l's x (l wave-uniform): two v_readlane_b32 into an SGPR pair
-__device__ __forceinline__ double readlane_d(double x, int l) {
-  const unsigned long long v = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-
 // Blocked by 4 columns (default): step j4 factorises the 4√ó4 diagonal tile in
 // its owner lane (j4, j4), the panel lanes (j4, tj > j4) / (ti > j4, j4) then
 // form their U / L pieces locally from it (U = L_dd‚Åª¬π¬∑A, L = A¬∑U_dd‚Åª¬π), and
@@ -537,19 +511,19 @@ __device__ __forceinline__ void tri_inv32(double* S, int o, int wv, int wl, int 
 #pragma unroll
     for (int jj = 1; jj < 16; ++jj)
       if (jj > c) S[(bo + jj) * SLD + bo + c] = x[jj];
-    d4n tm = {0, 0, 0, 0}, xm = {0, 0, 0, 0};
+    d4 tm = {0, 0, 0, 0}, xm = {0, 0, 0, 0};
 #pragma unroll
     for (int st = 0; st < 4; ++st) {   // T = L21 ¬∑ L11‚Åª¬π
       const int k = 4 * st + g;
       const double av = S[(o + 16 + l16) * SLD + o + k];
       const double bv = k == l16 ? 1.0 : (k > l16 ? S[(o + k) * SLD + o + l16] : 0.0);
-      tm = nmfma(av, bv, tm);
+      tm = mfma_f64(av, bv, tm);
     }
 #pragma unroll
     for (int st = 0; st < 4; ++st) {   // X21 = L22‚Åª¬π ¬∑ T
       const int k = 4 * st + g;
       const double av = l16 == k ? 1.0 : (l16 > k ? S[(o + 16 + l16) * SLD + o + 16 + k] : 0.0);
-      xm = nmfma(av, tm[st], xm);
+      xm = mfma_f64(av, tm[st], xm);
     }
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) S[(o + 16 + g + 4 * rr) * SLD + o + l16] = -xm[rr];
@@ -585,19 +559,19 @@ __device__ __forceinline__ void tri_inv32(double* S, int o, int wv, int wl, int 
 #pragma unroll
     for (int j = 0; j < 16; ++j)
       if (j >= c) S[(bo + c) * SLD + bo + j] = y[j];
-    d4n tm = {0, 0, 0, 0}, ym = {0, 0, 0, 0};
+    d4 tm = {0, 0, 0, 0}, ym = {0, 0, 0, 0};
 #pragma unroll
     for (int st = 0; st < 4; ++st) {   // T = U12 ¬∑ U22‚Åª¬π
       const int k = 4 * st + g;
       const double av = S[(o + l16) * SLD + o + 16 + k];
       const double bv = k <= l16 ? S[(o + 16 + k) * SLD + o + 16 + l16] : 0.0;
-      tm = nmfma(av, bv, tm);
+      tm = mfma_f64(av, bv, tm);
     }
 #pragma unroll
     for (int st = 0; st < 4; ++st) {   // Y12 = U11‚Åª¬π ¬∑ T
       const int k = 4 * st + g;
       const double av = l16 <= k ? S[(o + l16) * SLD + o + k] : 0.0;
-      ym = nmfma(av, tm[st], ym);
+      ym = mfma_f64(av, tm[st], ym);
     }
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) S[(o + g + 4 * rr) * SLD + o + 16 + l16] = -ym[rr];
@@ -619,7 +593,7 @@ __device__ __forceinline__ void dinv32(const double* S, int o, double* __restric
 // with A(i, k) / B(k, j) given by functors (lane: A row tr+l16, B column tc+l16)
 // (k-steps past `ns` skipped: ns wave-uniform, 4 or 8)
 template <class FA, class FB>
-__device__ __forceinline__ d4n tile32(int tr, int tc, FA A, FB Bm, int ns = 8) {
+__device__ __forceinline__ d4 tile32(int tr, int tc, FA A, FB Bm, int ns = 8) {
   const int lane = threadIdx.x & 63, g = lane >> 4, l16 = lane & 15;
   double av[8], bv[8];
 #pragma unroll
@@ -629,10 +603,10 @@ __device__ __forceinline__ d4n tile32(int tr, int tc, FA A, FB Bm, int ns = 8) {
       bv[s] = Bm(4 * s + g, tc + l16);
     }
   }
-  d4n acc = {0, 0, 0, 0};
+  d4 acc = {0, 0, 0, 0};
 #pragma unroll
   for (int s = 0; s < 8; ++s)
-    if (s < ns) acc = nmfma(av[s], bv[s], acc);
+    if (s < ns) acc = mfma_f64(av[s], bv[s], acc);
   return acc;
 }
 
@@ -751,9 +725,9 @@ __device__ __forceinline__ void diag_core(const DiagLds& L, double* __restrict__
     const int tr = (wv >> 1) * 16, tc = (wv & 1) * 16;
     const int i = tr + l16, j = tc + l16;
     // U_ab tile: k ‚â§ tr + 15 (L_aa‚Åª¬π is lower); L_ba tile: k ‚â§ tc + 15
-    const d4n au = tile32(tr, tc, [&](int, int k) { return k == i ? 1.0 : (k < i ? S[i * SLD + k] : 0.0); },
+    const d4 au = tile32(tr, tc, [&](int, int k) { return k == i ? 1.0 : (k < i ? S[i * SLD + k] : 0.0); },
                           [&](int k, int) { return S[k * SLD + 32 + j]; }, tr ? 8 : 4);
-    const d4n al = tile32(tr, tc, [&](int, int k) { return S[(32 + i) * SLD + k]; },
+    const d4 al = tile32(tr, tc, [&](int, int k) { return S[(32 + i) * SLD + k]; },
                           [&](int k, int) { return k <= j ? S[k * SLD + j] : 0.0; }, tc ? 8 : 4);
     __syncthreads();   // every wave has read A_ab / A_ba
     NLU_MARK(10);
@@ -781,7 +755,7 @@ __device__ __forceinline__ void diag_core(const DiagLds& L, double* __restrict__
   // only its own tile, the others read L_ba / U_ab)
   {
     const int tr = (wv >> 1) * 16, tc = (wv & 1) * 16;
-    d4n acc = tile32(tr, tc, [&](int i, int k) { return S[(32 + i) * SLD + k]; },
+    d4 acc = tile32(tr, tc, [&](int i, int k) { return S[(32 + i) * SLD + k]; },
                      [&](int k, int j) { return S[k * SLD + 32 + j]; });
 #pragma unroll
     for (int rr = 0; rr < 4; ++rr) {
@@ -817,7 +791,7 @@ __device__ __forceinline__ void diag_core(const DiagLds& L, double* __restrict__
   if (wv < 2) {
     tri_inv32(S, 32, wv, 0, 1);
   } else {
-    d4n acc[4];
+    d4 acc[4];
     if (wv == 2) {
 #pragma unroll
       for (int q = 0; q < 4; ++q)
@@ -846,7 +820,7 @@ __device__ __forceinline__ void diag_core(const DiagLds& L, double* __restrict__
   // ---- F. off-diagonal inverse blocks (two 16√ó16 tiles per wave), in place
   // of T_L / T_U
   {
-    d4n acc[2];
+    d4 acc[2];
 #pragma unroll
     for (int q = 0; q < 2; ++q) {
       const int tile = (wv & 1) * 2 + q;
@@ -910,15 +884,15 @@ __device__ __forceinline__ void diag_strip0(const double* S, double* __restrict_
   for (int s = 0; s < 16; ++s)
     av[s] = src_on ? kval(sv, r0 + 16 * wv + l16, c0 + 4 * s + g)
                    : Kb[(size_t)(r0 + 16 * wv + l16) * ld + c0 + 4 * s + g];
-  d4n acc[4];
+  d4 acc[4];
 #pragma unroll
   for (int ct = 0; ct < 4; ++ct) {   // U11‚Åª¬π is upper: k ‚â§ 16ct + 15
-    acc[ct] = (d4n){0, 0, 0, 0};
+    acc[ct] = (d4){0, 0, 0, 0};
     const int c = 16 * ct + l16;
 #pragma unroll
     for (int s = 0; s < 4 * (ct + 1); ++s) {
       const int k = 4 * s + g;
-      acc[ct] = nmfma(av[s], k <= c ? S[k * SLD + c] : 0.0, acc[ct]);
+      acc[ct] = mfma_f64(av[s], k <= c ? S[k * SLD + c] : 0.0, acc[ct]);
     }
   }
   int over = 0;
@@ -952,12 +926,12 @@ __device__ __forceinline__ void diag_strip0(const double* S, double* __restrict_
   for (int s = 0; s < 16; ++s) bv[s] = bsrc[(size_t)4 * s * ld];
 #pragma unroll
   for (int it = 0; it < 4; ++it) {   // L11‚Åª¬π is unit lower: k ‚â§ 16it + 15
-    acc[it] = (d4n){0, 0, 0, 0};
+    acc[it] = (d4){0, 0, 0, 0};
     const int i = 16 * it + l16;
 #pragma unroll
     for (int s = 0; s < 4 * (it + 1); ++s) {
       const int k = 4 * s + g;
-      acc[it] = nmfma(k == i ? 1.0 : (k < i ? S[i * SLD + k] : 0.0), bv[s], acc[it]);
+      acc[it] = mfma_f64(k == i ? 1.0 : (k < i ? S[i * SLD + k] : 0.0), bv[s], acc[it]);
     }
   }
   over = 0;
@@ -1098,15 +1072,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     }
     __syncthreads();
     if (!sym && !wact) return;
-    d4n acc[4];
+    d4 acc[4];
     int over = 0;
     if (wact) {
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
-        acc[ct] = (d4n){0, 0, 0, 0};
+        acc[ct] = (d4){0, 0, 0, 0};
 #pragma unroll
         for (int s = 0; s < 4 * (ct + 1); ++s)
-          acc[ct] = nmfma(av[s], X[(4 * s + g) * TLD + 16 * ct + l16], acc[ct]);
+          acc[ct] = mfma_f64(av[s], X[(4 * s + g) * TLD + 16 * ct + l16], acc[ct]);
       }
 #pragma unroll
       for (int ct = 0; ct < 4; ++ct) {
@@ -1172,15 +1146,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
       for (int u = 0; u < 8; ++u) X[k * TLD + c8 + u] = ok ? v[8 * h + u] : 0.0;
     }
     __syncthreads();
-    d4n acc[4];
+    d4 acc[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = (d4n){0, 0, 0, 0};
+    for (int q = 0; q < 4; ++q) acc[q] = (d4){0, 0, 0, 0};
     const int ns = 4 * (wv + 1);
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       if (s < ns) {   // wave-uniform
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = nmfma(av[s], X[(4 * s + g) * TLD + 16 * q + l16], acc[q]);
+        for (int q = 0; q < 4; ++q) acc[q] = mfma_f64(av[s], X[(4 * s + g) * TLD + 16 * q + l16], acc[q]);
       }
     }
     int over = 0;
@@ -1296,9 +1270,9 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
       // the A operand a[] grows as av[] shrinks
 #pragma unroll
       for (int ct = 3; ct >= 0; --ct) {
-        d4n lt = {0, 0, 0, 0};
+        d4 lt = {0, 0, 0, 0};
 #pragma unroll
-        for (int s = 0; s < 4 * (ct + 1); ++s) lt = nmfma(X[(4 * s + g) * TLD + 16 * ct + l16], av[s], lt);
+        for (int s = 0; s < 4 * (ct + 1); ++s) lt = mfma_f64(X[(4 * s + g) * TLD + 16 * ct + l16], av[s], lt);
         __builtin_amdgcn_sched_barrier(0);   // one column tile's LDS reads in flight at a time
 #pragma unroll
         for (int rr = 0; rr < 4; ++rr) {
@@ -1334,15 +1308,15 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     }
     stage(v);
     __syncthreads();
-    d4n um[4];
+    d4 um[4];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) um[q] = (d4n){0, 0, 0, 0};
+    for (int q = 0; q < 4; ++q) um[q] = (d4){0, 0, 0, 0};
     const int ns = 4 * (wv + 1);
 #pragma unroll
     for (int s = 0; s < 16; ++s) {
       if (s < ns) {   // wave-uniform
 #pragma unroll
-        for (int q = 0; q < 4; ++q) um[q] = nmfma(al[s], X[(4 * s + g) * TLD + 16 * q + l16], um[q]);
+        for (int q = 0; q < 4; ++q) um[q] = mfma_f64(al[s], X[(4 * s + g) * TLD + 16 * q + l16], um[q]);
       }
     }
     if (wact) {   // L21(0) rows (diagonal launch)
@@ -1372,7 +1346,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     }
     stage(u);
   }
-  d4n acc[4];
+  d4 acc[4];
   if (wact) {
 #pragma unroll
     for (int q = 0; q < 4; ++q) {
@@ -1418,7 +1392,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
 #pragma unroll
     for (int q = 0; q < 4; ++q) bq[q] = X[(4 * s + g) * TLD + 16 * q + l16];
 #pragma unroll
-    for (int q = 0; q < 4; ++q) acc[q] = nmfma(a[s], bq[q], acc[q]);
+    for (int q = 0; q < 4; ++q) acc[q] = mfma_f64(a[s], bq[q], acc[q]);
   }
 #pragma unroll
   for (int q = 0; q < 4; ++q) {
@@ -1489,7 +1463,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
     }
   };
   double a[NB64 / 4];
-  d4n acc[4];
+  d4 acc[4];
   stage(c0);
   if (wact) {
     const double* arow = Kb + (size_t)(rbase + l16) * ld + c0;
@@ -1515,7 +1489,7 @@ __global__ __launch_bounds__(256) __attribute__((amdgpu_waves_per_eu(4))) void n
 #pragma unroll
         for (int q = 0; q < 4; ++q) bq[q] = U[(4 * s + g) * ULD + 16 * q + l16];
 #pragma unroll
-        for (int q = 0; q < 4; ++q) acc[q] = nmfma(a[s], bq[q], acc[q]);
+        for (int q = 0; q < 4; ++q) acc[q] = mfma_f64(a[s], bq[q], acc[q]);
       }
     }
     if (half == 1) break;
@@ -1835,9 +1809,9 @@ __device__ __forceinline__ void ldiag_body(
   // 2, 2 per wave; rows ra / rb = 3 of the 4√ó4 tile grid), mirrored through
   // LDS afterwards:
   //   w0: (0,0) (3,0) (3,1)   w1: (1,0) (1,1) (3,2)   w2: (2,0) (2,1)   w3: (2,2) (3,3)
-  d4n accd[3];
+  d4 accd[3];
 #pragma unroll
-  for (int q = 0; q < 3; ++q) accd[q] = (d4n){0, 0, 0, 0};
+  for (int q = 0; q < 3; ++q) accd[q] = (d4){0, 0, 0, 0};
   double sweep = 0.0;   // t < 64: Œ£ L(J, <J)[t]¬∑y (w0); 64 ‚â§ t < 128: Œ£ L(J, <J)[t ‚àí 64]¬∑(d‚àòz) (w1)
   const int ra = wv < 3 ? wv : 2;                       // row of tile 0 (and tile 1 on w1 / w2)
   const int tc0 = wv == 3 ? 2 : 0;                      // column of tile 0 (row ra)
@@ -1868,9 +1842,9 @@ __device__ __forceinline__ void ldiag_body(
         const double* row = S + (4 * s + g) * TLD + l16;
         const double aa = row[16 * ra] * dk[s];
         const double ab = bact ? row[48] * dk[s] : 0.0;
-        accd[0] = nmfma(aa, row[16 * tc0], accd[0]);
-        if (!t1b || bact) accd[1] = nmfma(t1b ? ab : aa, row[16 * tc1], accd[1]);
-        if (wv < 2 && bact) accd[2] = nmfma(ab, row[16 * tc2], accd[2]);
+        accd[0] = mfma_f64(aa, row[16 * tc0], accd[0]);
+        if (!t1b || bact) accd[1] = mfma_f64(t1b ? ab : aa, row[16 * tc1], accd[1]);
+        if (wv < 2 && bact) accd[2] = mfma_f64(ab, row[16 * tc2], accd[2]);
       }
     }
     if (swp) {   // forward sweeps: the row strip times the finished blocks of y / z
@@ -1884,7 +1858,7 @@ __device__ __forceinline__ void ldiag_body(
   __syncthreads();   // the staging is consumed: S becomes the diagonal image
   LD_MARK(1);
   if (c0 > 0) {   // workgroup-uniform: X's tiles and their mirrors ‚Üí S
-    auto put = [&](int r, int c, const d4n& x) {
+    auto put = [&](int r, int c, const d4& x) {
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) {
         const int i = 16 * r + g + 4 * rr, j = 16 * c + l16;
@@ -2109,9 +2083,9 @@ __device__ __forceinline__ void lcol_body(double* X, int b, int it, double* __re
   const double pr = inr ? rr_ : 1.0;                     // p_i of this lane's tile row (growth bound)
   src_stage_codes(src, sv, X, r0, c0);
   if (t < 2 * NB64) X[LC_P + t] = pv;   // LC_UD = LC_P + 64
-  d4n acc[4];
+  d4 acc[4];
 #pragma unroll
-  for (int q = 0; q < 4; ++q) acc[q] = (d4n){0, 0, 0, 0};
+  for (int q = 0; q < 4; ++q) acc[q] = (d4){0, 0, 0, 0};
   auto stage = [&](int st) {
     if (!wact) return;
     const double* TI = X + (st & 1) * LC_STAGE;
@@ -2122,7 +2096,7 @@ __device__ __forceinline__ void lcol_body(double* X, int b, int it, double* __re
       const int k = 4 * kk + g;
       const double bo = TI[lc_off(16 * wv + l16, k)] * DS[k];   // L(I)[i][k]¬∑d_k
 #pragma unroll
-      for (int c = 0; c < 4; ++c) acc[c] = nmfma(SI[lc_off(16 * c + l16, k)], bo, acc[c]);
+      for (int c = 0; c < 4; ++c) acc[c] = mfma_f64(SI[lc_off(16 * c + l16, k)], bo, acc[c]);
     }
   };
   for (int st = 0; st + 1 < nst; ++st) {
@@ -2161,19 +2135,19 @@ __device__ __forceinline__ void lcol_body(double* X, int b, int it, double* __re
   if (!wact) return;   // no barrier below
   // L(I, J)·µÄ block a = Œ£_{c ‚â§ a} U‚Åª·µÄ(a, c)¬∑C·µÄ(c, w): A operand U‚Åª¬π[j][j'] (j = 16c + 4s + g,
   // j' = 16a + l16; zero below the diagonal), B operand C·µÄ's register s of block c
-  d4n lt[4];
+  d4 lt[4];
   int over = 0;
   const double bound = growth_bound(__hip_atomic_load(kamax + b, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT));
 #pragma unroll
   for (int a = 0; a < 4; ++a) {
-    lt[a] = (d4n){0, 0, 0, 0};
+    lt[a] = (d4){0, 0, 0, 0};
 #pragma unroll
     for (int c = 0; c <= a; ++c)
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const int j = 16 * c + 4 * s + g, jp = 16 * a + l16;
         const double u = X[lc_uoff(j, jp)];
-        lt[a] = nmfma(c < a || j <= jp ? u : 0.0, acc[c][s], lt[a]);
+        lt[a] = mfma_f64(c < a || j <= jp ? u : 0.0, acc[c][s], lt[a]);
       }
   }
   const int ri = 16 * wv + l16;

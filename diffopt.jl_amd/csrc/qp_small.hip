@@ -25,7 +25,7 @@
 // the call runs the batched route instead, which also reports singularities in
 // the reference's coordinates.  Same semantics, different rounding: the
 // outputs agree with the batched route and the oracle to the parity bar.
-#include "dopt_internal.h"
+#include "device_prims.h"
 #include <type_traits>
 
 namespace dopt {
@@ -251,13 +251,7 @@ __device__ __forceinline__ void sm_lu_from(double (&e)[8][8], SmallLds& L, int N
 #pragma unroll
       for (int i = 0; i < SM_GB; ++i)
 #pragma unroll
-        for (int j = 0; j < SM_GB; ++j) {
-          const long long bits = __double_as_longlong(e[KK][KK]);
-          const int src = 16 * i + SM_GB * g + j;
-          d[i * SM_GB + j] = __longlong_as_double(
-              ((long long)__builtin_amdgcn_readlane((int)(bits >> 32), src) << 32) |
-              (unsigned)__builtin_amdgcn_readlane((int)bits, src));
-        }
+        for (int j = 0; j < SM_GB; ++j) d[i * SM_GB + j] = readlane_d(e[KK][KK], 16 * i + SM_GB * g + j);
 #pragma unroll
       for (int q = 0; q < SM_GB; ++q) {
         const double rq = 1.0 / d[q * SM_GB + q];
@@ -355,23 +349,6 @@ __device__ __forceinline__ void sm_lu_from(double (&e)[8][8], SmallLds& L, int N
 }
 
 // lane l's x (l wave-uniform): two v_readlane_b32 into an SGPR pair
-__device__ __forceinline__ double sm_readlane(double x, int l) {
-  const unsigned long long v = (unsigned long long)__double_as_longlong(x);
-  const unsigned lo = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)v, l);
-  const unsigned hi = (unsigned)__builtin_amdgcn_readlane((int)(unsigned)(v >> 32), l);
-  return __longlong_as_double((long long)(((unsigned long long)hi << 32) | lo));
-}
-__device__ __forceinline__ double sm_rcp(double d) {   // v_rcp_f64 + two Newton steps
-  double r = __builtin_amdgcn_rcp(d);
-  r = fma(fma(-d, r, 1.0), r, r);
-  return fma(fma(-d, r, 1.0), r, r);
-}
-__device__ __forceinline__ void sm_wave_sync() {
-  __builtin_amdgcn_fence(__ATOMIC_RELEASE, "wavefront");
-  __builtin_amdgcn_wave_barrier();
-  __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "wavefront");
-}
-typedef double sm_d4 __attribute__((ext_vector_type(4)));
 
 // Right-looking no-pivot LU by 16-blocks over the LDS image (round 6, VERDICT
 // r05 item 5; default — -DSM_LU_GROUPS builds the rank-4 groups above), the
@@ -445,7 +422,7 @@ __device__ __forceinline__ void sm_lu_blocked(SmallLds& L, int N, int NB, double
     for (int k = 0; k < 16; ++k) {
       double pr[16];
 #pragma unroll
-      for (int j = k; j < 16; ++j) pr[j] = sm_readlane(a[j], k);
+      for (int j = k; j < 16; ++j) pr[j] = readlane_d(a[j], k);
       // 1/u_kk by v_rcp_f64 and two Newton steps, the rows at or above k
       // untouched by a zero multiplier (no branch on the chain; the IEEE
       // division and a branch measured 35.1 k against 29.9 k cycles per
@@ -461,7 +438,7 @@ __device__ __forceinline__ void sm_lu_blocked(SmallLds& L, int N, int NB, double
     // the forward sweep's block: y_k from lane k once final, the rows below it
 #pragma unroll
     for (int k = 0; k < 16; ++k) {
-      const double yk = sm_readlane(rv, k);
+      const double yk = readlane_d(rv, k);
       if (lane > k) rv = fma(-a[k], yk, rv);
     }
     // the tests and the stores of row r's entries (r, k0 + j): the rows below
@@ -489,7 +466,7 @@ __device__ __forceinline__ void sm_lu_blocked(SmallLds& L, int N, int NB, double
     if (lane < 16)
 #pragma unroll
       for (int j = 0; j < 16; ++j) Lw[16 * j + lane] = j < lane ? a[j] : 0.0;
-    sm_wave_sync();
+    wave_sync();
     SB_LAP(0);
     // ---- U row: columns k0 + 16 + q, each wave a contiguous quarter of them
     // (lane ↔ column: conflict-free LDS rows; q = wv + 4·lane, eight lanes
@@ -538,14 +515,14 @@ __device__ __forceinline__ void sm_lu_blocked(SmallLds& L, int N, int NB, double
     const int nt = NB - KK - 1;
     for (int tt = wv; tt < nt * nt; tt += SM_T / 64) {
       const int i0 = k0 + 16 + 16 * (tt / nt), j0 = k0 + 16 + 16 * (tt % nt);
-      sm_d4 acc;
+      d4 acc;
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) acc[rr] = S[(i0 + g + 4 * rr) * SM_LD + j0 + l16];
 #pragma unroll
       for (int s = 0; s < 4; ++s) {
         const double av = -S[(i0 + l16) * SM_LD + k0 + 4 * s + g];
         const double bv = S[(k0 + 4 * s + g) * SM_LD + j0 + l16];
-        acc = __builtin_amdgcn_mfma_f64_16x16x4f64(av, bv, acc, 0, 0, 0);
+        acc = mfma_f64(av, bv, acc);
       }
 #pragma unroll
       for (int rr = 0; rr < 4; ++rr) S[(i0 + g + 4 * rr) * SM_LD + j0 + l16] = acc[rr];
@@ -604,10 +581,7 @@ __device__ __forceinline__ void sm_sweep_phase(const double* S, const double* di
     for (int q = 0; q < 4; ++q) {
       if (it + q < cnt) {   // uniform
         const int kq = k + q * st;
-        const double src = HI ? y1 : y0;
-        double v = __longlong_as_double(
-            ((long long)__builtin_amdgcn_readlane((int)(__double_as_longlong(src) >> 32), kq & 63) << 32) |
-            (unsigned)__builtin_amdgcn_readlane((int)__double_as_longlong(src), kq & 63));
+        double v = readlane_d(HI ? y1 : y0, kq & 63);
         if (DIAG) v *= dv[q];
         if (M0 == 1) y0 = fma(-c0[q], v, y0);
         if (M0 == 2) y0 = (LOWER ? i0 > kq : i0 < kq) ? fma(-c0[q], v, y0) : y0;
@@ -687,7 +661,7 @@ __device__ __forceinline__ void sm_uinv(const double* S, int NB, double (*U)[16 
     double acc = x[j];
 #pragma unroll
     for (int q = 0; q < j; ++q, ++e) acc = fma(-x[q], uv[e], acc);
-    x[j] = acc * sm_rcp(uv[e++]);
+    x[j] = acc * rcp_nr(uv[e++]);
   }
 #pragma unroll
   for (int j = 0; j < 16; ++j) U[KK][i * 17 + j] = x[j];
@@ -705,7 +679,7 @@ __device__ __forceinline__ void sm_usolve_blk(const double* S, const double (*U)
     const int i = lane - base;
     const bool inb = i >= 0 && i < 16;
     if (inb) sc[i] = hi ? y1 : y0;
-    sm_wave_sync();
+    wave_sync();
     const double* ur = U[KK] + (inb ? i : 0) * 17;
     double x0 = 0.0, x1 = 0.0;
 #pragma unroll
@@ -713,14 +687,14 @@ __device__ __forceinline__ void sm_usolve_blk(const double* S, const double (*U)
       x0 = fma(ur[j], sc[j], x0);
       x1 = fma(ur[j + 1], sc[j + 1], x1);
     }
-    sm_wave_sync();
+    wave_sync();
     if (inb) {
       const double x = x0 + x1;
       sc[i] = x;
       if (hi) y1 = x;
       else y0 = x;
     }
-    sm_wave_sync();
+    wave_sync();
     if (k0 == 0) break;
     const double* r0 = S + lane * SM_LD + k0;
     const double* r1 = S + (64 + lane) * SM_LD + k0;
@@ -736,7 +710,7 @@ __device__ __forceinline__ void sm_usolve_blk(const double* S, const double (*U)
     }
     if (lane < k0) y0 -= a0 + a1;
     if (64 + lane < k0) y1 -= c0 + c1;
-    sm_wave_sync();
+    wave_sync();
   }
 }
 #endif
@@ -863,7 +837,7 @@ __device__ __forceinline__ void sm_reverse(const QPIn& P, const double* __restri
     sm_usolve_blk(S, L.uinv, (N + SM_G - 1) / SM_G, lane, y0, y1, L.dinv);
 #else
     for (int r = lane; r < N; r += 64) L.dinv[r] = 1.0 / S[r * SM_LD + r];
-    sm_wave_sync();
+    wave_sync();
     sm_usolve(S, L.dinv, N, lane, y0, y1);
 #endif
     if (lane < N) y[lane] = y0;

@@ -31,13 +31,14 @@
 // (DESIGN.md §4): HBM-bound, no MFMA.
 #include <hipcub/hipcub.hpp>
 
-#include "dopt_internal.h"
+#include "device_prims.h"
+#include "lsqr_core.h"
 
 namespace dopt {
 
 namespace {
 
-constexpr int SP_TPB = 1024;   // LSQR workgroup (16 waves)
+constexpr int SP_TPB = 1024;   // LSQR workgroup (16 waves: sp_block_sum)
 // lanes per output entry of a product: a template parameter chosen per batch
 // from the mean entries per output (sp_lanes): 1 for the usual few-per-row
 // sparsity (every lane its own row, the row's loads pipelined), 4 / 16 for
@@ -203,8 +204,7 @@ __global__ __launch_bounds__(SP_SETUP) void sp_fwd_rhs_kernel(
         const double* col = dA + b * p * n + (size_t)j * p;
         for (int k = lane; k < p; k += 64) acc = fma(col[k], nu[b * p + k], acc);
       }
-#pragma unroll
-      for (int o = 32; o > 0; o >>= 1) acc += __shfl_xor(acc, o);
+      acc = wave_sum(acc);
       if (lane == 0) r[j] += acc;
     }
   // λ block: λ∘(dG z) − λ∘dh
@@ -287,18 +287,15 @@ __device__ void sp_matvec(const SpSys& S, size_t b, int tr, const double* __rest
   __syncthreads();
 }
 
-__device__ __forceinline__ double sp_block_sum(double v, double* red) {
-#pragma unroll
-  for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o);
-  const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
-  __syncthreads();
-  if (lane == 0) red[wv] = v;
-  __syncthreads();
-  double r = 0.0;
-#pragma unroll
-  for (int w = 0; w < SP_TPB / 64; ++w) r += red[w];
-  return r;
-}
+// LHS (tr = 0) or LHSᵀ of problem b as lsqr_solve's operator
+template <int SP_G>
+struct SpLHS {
+  const SpSys& S;
+  size_t b;
+  int tr;
+  __device__ __forceinline__ void mul(const double* v, double* out) const { sp_matvec<SP_G>(S, b, tr, v, out); }
+  __device__ __forceinline__ void tmul(const double* u, double* out) const { sp_matvec<SP_G>(S, b, !tr, u, out); }
+};
 
 // blockIdx.x = problem, blockIdx.y = sequence q (0: reverse, LHS; 1: forward,
 // LHSᵀ — `dir` gives each sequence's operator, rhs / out / info per sequence);
@@ -322,112 +319,14 @@ __global__ __launch_bounds__(SP_TPB) void sp_lsqr_kernel(SpSys S, int B, int dir
   double* v = u + N;
   double* w = v + N;
   double* tmp = w + N;
-  double bb = 0.0;
-  for (int i = t; i < N; i += SP_TPB) {
-    const double r = rhs[b * N + i];
-    u[i] = r;
-    x[i] = 0.0;
-    bb = fma(r, r, bb);
-  }
-  double beta = sqrt(sp_block_sum(bb, red));
-  int it = 0, istop = 0;
-  if (beta > 0.0) {
-    for (int i = t; i < N; i += SP_TPB) u[i] /= beta;
-    __syncthreads();
-    sp_matvec<SP_G>(S, b, !trans, u, v);   // v = Aᵀu
-    double aa = 0.0;
-    for (int i = t; i < N; i += SP_TPB) aa = fma(v[i], v[i], aa);
-    double alpha = sqrt(sp_block_sum(aa, red));
-    if (alpha > 0.0) {
-      for (int i = t; i < N; i += SP_TPB) {
-        v[i] /= alpha;
-        w[i] = v[i];
-      }
-      __syncthreads();
-      const double eps = 2.220446049250313e-16;
-      const double atol = sqrt(eps), btol = sqrt(eps), ctol = sqrt(eps);
-      double anorm = 0.0, ddnorm = 0.0, res2 = 0.0, xxnorm = 0.0, zz = 0.0;
-      double sn2 = 0.0, cs2 = -1.0, rhobar = alpha, phibar = beta;
-      const double bnorm = beta;
-      const int maxiter = N;
-      while (it < maxiter) {
-        ++it;
-        sp_matvec<SP_G>(S, b, trans, v, tmp);   // tmp = A v
-        double su = 0.0;
-        for (int i = t; i < N; i += SP_TPB) {
-          const double ui = tmp[i] - alpha * u[i];
-          u[i] = ui;
-          su = fma(ui, ui, su);
-        }
-        beta = sqrt(sp_block_sum(su, red));
-        if (beta > 0.0) {
-          for (int i = t; i < N; i += SP_TPB) u[i] /= beta;
-          __syncthreads();
-          anorm = sqrt(anorm * anorm + alpha * alpha + beta * beta);
-          sp_matvec<SP_G>(S, b, !trans, u, tmp);   // tmp = Aᵀu
-          double sv = 0.0;
-          for (int i = t; i < N; i += SP_TPB) {
-            const double vi = tmp[i] - beta * v[i];
-            v[i] = vi;
-            sv = fma(vi, vi, sv);
-          }
-          alpha = sqrt(sp_block_sum(sv, red));
-          if (alpha > 0.0)
-            for (int i = t; i < N; i += SP_TPB) v[i] /= alpha;
-          __syncthreads();
-        }
-        const double rhobar1 = rhobar;
-        const double rho = hypot(rhobar1, beta);
-        const double cs = rhobar1 / rho, sn = beta / rho;
-        const double theta = sn * alpha;
-        rhobar = -cs * alpha;
-        const double phi = cs * phibar;
-        phibar = sn * phibar;
-        const double tau = sn * phi;
-        const double t1 = phi / rho, t2 = -theta / rho;
-        double sw = 0.0;
-        for (int i = t; i < N; i += SP_TPB) {
-          const double wi = w[i];
-          sw = fma(wi, wi, sw);
-          x[i] = x[i] + t1 * wi;
-          w[i] = v[i] + t2 * wi;
-        }
-        ddnorm += sp_block_sum(sw, red) / (rho * rho);
-        const double delta = sn2 * rho, gambar = -cs2 * rho;
-        const double rhs_ = phi - delta * zz;
-        const double zbar = rhs_ / gambar;
-        const double xnorm = sqrt(xxnorm + zbar * zbar);
-        const double gamma = hypot(gambar, theta);
-        cs2 = gambar / gamma;
-        sn2 = theta / gamma;
-        zz = rhs_ / gamma;
-        xxnorm += zz * zz;
-        const double acond = anorm * sqrt(ddnorm);
-        const double rnorm = sqrt(phibar * phibar + res2);
-        const double arnorm = alpha * fabs(tau);
-        const double test1 = rnorm / bnorm;
-        const double test2 = (anorm * rnorm != 0.0) ? arnorm / (anorm * rnorm) : 0.0;
-        const double test3 = (acond != 0.0) ? 1.0 / acond : 0.0;
-        const double t1r = test1 / (1.0 + anorm * xnorm / bnorm);
-        const double rtol = btol + atol * anorm * xnorm / bnorm;
-        istop = 0;
-        if (it >= maxiter) istop = 7;
-        if (1.0 + test3 <= 1.0) istop = 6;
-        if (1.0 + test2 <= 1.0) istop = 5;
-        if (1.0 + t1r <= 1.0) istop = 4;
-        if (test3 <= ctol) istop = 3;
-        if (test2 <= atol) istop = 2;
-        if (test1 <= rtol) istop = 1;
-        __syncthreads();
-        if (istop) break;
-      }
-    }
-  }
+  const SpLHS<SP_G> op{S, b, trans};
+  LsqrScalars st;
+  lsqr_solve<SP_TPB, sp_block_sum>(st, op, rhs + b * N, 0.0, N, x, u, v, w, tmp, N, red);
   __syncthreads();
   for (int i = t; i < N; i += SP_TPB) xo[b * N + i] = -x[i];
   if (t == 0 && info) {
-    info[2 * b] = istop;
-    info[2 * b + 1] = it;
+    info[2 * b] = st.istop;
+    info[2 * b + 1] = st.it;
   }
 }
 

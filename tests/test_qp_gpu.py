@@ -524,6 +524,9 @@ def test_lp_iterative_batch_mixed_with_qp(QPBatch, lu_mode):
         rz, rl, rn = oqp.reverse_differentiate(Qs[b], a["G"], a["h"], np.zeros((0, n)),
                                                a["z"], a["lam"], np.zeros(0), a["dzb"])
         assert relfro(rev[b], np.concatenate([rz, rl, rn])) <= RTOL
+    # a zero seed: LSQR's β = 0 exit (problem 0) and the LU solve (problem 1) both return exact zeros
+    rev0 = np.asarray(e.reverse(np.zeros((2, n))))
+    assert rev0.shape == np.asarray(rev).shape and np.all(rev0 == 0)
 
 
 def test_lsqr_branch_beyond_lds_size(QPBatch):

@@ -79,11 +79,16 @@ def test_sparse_route_matches_dense_route():
     of the products differs, so they agree far below the 1e-6 bar."""
     from diffopt_amd.synthetic import lp_sparse_numpy
     d = lp_sparse_numpy(2, 120, 10, 80, 3, 102)
-    rs, fs = _batch(d, sparse=True).forward_reverse(d["dl_dz"], dq=d["dq"], dh=d["dh"], db=d["db"])
+    es = _batch(d, sparse=True)
+    rs, fs = es.forward_reverse(d["dl_dz"], dq=d["dq"], dh=d["dh"], db=d["db"])
     rd, fd = _batch(d, sparse=False).forward_reverse(d["dl_dz"], dq=d["dq"], dh=d["dh"], db=d["db"])
     for b in range(2):
         assert relfro(rs[b], rd[b]) <= 1e-7
         assert relfro(fs[b], fd[b]) <= 1e-7
+    # a zero seed: LSQR's β = 0 exit returns exact zeros, istop = 0 after 0 iterations
+    r0 = np.asarray(es.reverse(np.zeros_like(d["dl_dz"])))
+    assert r0.shape == np.asarray(rs).shape and np.all(r0 == 0)
+    assert np.all(es.lsqr_stats()[:, 0, :] == 0)
 
 
 def test_sparse_lp_above_dense_cap():
