@@ -53,8 +53,8 @@ def _check(d, e=None):
     for b in range(d["z"].shape[0]):
         orv, ofw, (itr, isr), (itf, isf) = _oracle(d, b)
         worst = max(worst, relfro(rev[b], orv), relfro(fwd[b], ofw))
-        assert stats[b, 0, 0] in (1, 2) and stats[b, 1, 0] in (1, 2), stats[b]   # converged, as the oracle
         assert isr in (1, 2) and isf in (1, 2)
+        assert stats[b, 0, 0] == isr and stats[b, 1, 0] == isf, (b, stats[b], isr, isf)   # the oracle's stop codes
     assert worst <= RTOL, worst
     return e, rev, fwd
 
@@ -227,7 +227,7 @@ def _conic_vs_oracle(d, cones, B, res, st, minnorm=False):
         ref = _oracle_outputs(cache, d["dA"][b], d["db"][b], d["dc"][b], d["dx"][b])
         fi, ri = ref["info"]
         assert fi[1] in (1, 2) and ri[1] in (1, 2), (b, fi, ri)
-        assert st["fwd_istop"][b] in (1, 2) and st["istop"][b] in (1, 2), st
+        assert (st["fwd_istop"][b], st["istop"][b]) == (fi[1], ri[1]), (b, st, fi, ri)   # the oracle's stop codes
         err = _errors(dict(fwd=out[b], dx=fdx[b], g=g[b], dA=dA[b], db=db[b], dc=dc[b]), ref, cache)
         if minnorm and max(err.values()) > RTOL:
             mn = _minnorm_judge(cache, d, b, out[b], g[b], ref)
