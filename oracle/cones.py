@@ -22,7 +22,9 @@ Cone codes (shared with ``include/diffopt_mi355x.h``):
     S²J as also fitting; the PSD+POS fixture, whose LSQR stops at maxiter,
     rules it out: max |Δdx| 4.45 vs 0.019 at atol 0.3.)
   Nonnegatives at exactly v = 0 gives 0.5 (MOSD's formula as recalled; the
-  value is parity-unpinned, generators keep a guard band away from 0).
+  reference's own value is parity-unpinned and the generators keep a guard
+  band away from 0; that the engine gives this oracle's 0.5 there is tested,
+  tests/cone_edge_cases.py's "ints" cones with y = s).
 """
 
 import math

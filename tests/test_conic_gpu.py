@@ -9,7 +9,14 @@ bench shape, the PSD+POS fixture), the oracle itself moves by ≫ 1e-6 under a
 1-ulp perturbation of its inputs, so no implementation can meet 1e-6; such
 an output is held to 10× the oracle's own 1-ulp spread instead ("relaxed").
 Every test reports how many outputs were judged under the relaxed bar and
-asserts its cap (0 for the well-posed shapes)."""
+asserts its cap (0 for the well-posed shapes).
+
+What pins Dπ itself: the shapes here see it through whole solves at 1e-6; the
+branches of conic_cone_kernel and dpi_apply that these generators never reach
+(exact SOC boundaries, one-signed, clustered and diagonal PSD spectra, sides
+63–66 and 256–257, v = 0, empty cones, tables above 128 and 256 cones) run in
+test_cone_edges_gpu.py, capped as test_capped_lsqr_istop7 is and held to
+≈ 1e-12."""
 
 import json
 import os
