@@ -4,6 +4,7 @@
 #include <chrono>
 #include <cstdlib>
 #include <cstring>
+#include <initializer_list>
 
 #include "dopt_internal.h"
 
@@ -86,6 +87,36 @@ struct Timer {
     return std::chrono::duration<double>(std::chrono::steady_clock::now() - t0).count();
   }
 };
+
+// One conic call through the staging buffers.  `in` / `out` list the arrays
+// that take part: the caller's pointer (host or device by the handle's
+// memory mode; null: absent), its slot in tin[] / tout[], and its doubles per
+// seed; k seeds scale every count.  `call` gets the device pointers in list
+// order; the outputs are copied back and the stream drained after it.
+struct ConicIn {
+  const double* p;
+  int slot;
+  size_t count;
+};
+struct ConicOut {
+  double* p;
+  int slot;
+  size_t count;
+};
+template <class F>
+void conic_call(Handle& h, size_t k, std::initializer_list<ConicIn> in, std::initializer_list<ConicOut> out,
+                F&& call) {
+  const double* ip[4];
+  double* op[6];
+  int i = 0;
+  for (const ConicIn& a : in) ip[i++] = stage_in(h, h.tin[a.slot], a.p, k * a.count);
+  i = 0;
+  for (const ConicOut& a : out) op[i++] = out_ptr(h, h.tout[a.slot], a.p, k * a.count);
+  call(ip, op);
+  i = 0;
+  for (const ConicOut& a : out) copy_out(h, a.p, op[i++], k * a.count);
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+}
 
 }  // namespace
 
@@ -1390,9 +1421,8 @@ static void conic_set_common(Handle* h, const double* A, const double* b, const 
     if (code < 0 || code > DOPT_CONE_PSD_TRI || dim < 0) throw Error(-1, "bad cone code/dimension");
     if (code == DOPT_CONE_SOC && dim < 1) throw Error(-1, "SecondOrderCone dimension must be >= 1");
     if (code == DOPT_CONE_PSD_TRI) {
-      int d = 0;
-      while (d * (d + 1) / 2 < dim) ++d;
-      if (d * (d + 1) / 2 != dim) throw Error(-1, "PSD triangle dimension is not triangular");
+      const int d = dopt::psd_side(dim);
+      if (dopt::psd_tri_dim(d) != dim) throw Error(-1, "PSD triangle dimension is not triangular");
       if (d > 4096) throw Error(-1, "PSD cones larger than 4096×4096 are not supported");
     }
     rows += dim;
@@ -1445,30 +1475,25 @@ int dopt_conic_set_csc(dopt_handle* h, const int64_t* A_colptr, const int64_t* A
     const int64_t* cp = stage_in_i64(*h, h->csc_in[0], A_colptr, B * (n + 1));
     const int64_t* rv = stage_in_i64(*h, h->csc_in[1], A_rowval, (size_t)A_nnz);
     const double* nz = stage_in(*h, h->csc_in_val[0], A_nzval, (size_t)A_nnz);
+    const double* A = nullptr;
     if (h->sparse) {   // A_moi kept sparse: CSC + its CSR copy (sparse.hip), no dense A
       for (int k = 0; k < ncones && cone_desc; ++k)
-        if (cone_desc[2 * k] == DOPT_CONE_PSD_TRI && cone_desc[2 * k + 1] > 64 * 65 / 2)
+        if (cone_desc[2 * k] == DOPT_CONE_PSD_TRI && cone_desc[2 * k + 1] > dopt::psd_tri_dim(64))
           throw Error(-1, "sparse conic route: PSD cones up to side 64 (their Dπ apply runs in LDS)");
-      h->cset = h->cfactored = false;
       if (m) dopt::sp_stage(*h, 0, cp, rv ? rv : cp, nz, A_nnz, (int)m, h->csc_err.as<int>());
-      int herr = 0;
-      DOPT_CHECK_HIP(hipMemcpyAsync(&herr, h->csc_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      if (herr) throw Error(-1, (herr & 1) ? "CSC colptr is not monotone / out of range"
-                                           : "CSC rowval out of range");
-      conic_set_common(h, nullptr, b, c, x, s, y, cone_desc, ncones);
-      return 0;
+    } else {
+      DevBuf& d = h->own_cin[0];
+      d.ensure(std::max<size_t>(B * m * n, 1) * sizeof(double));
+      if (m) dopt::csc_to_dense(*h, cp, rv ? rv : cp, nz ? nz : d.as<double>(), A_nnz, (int)m, (int)n,
+                                d.as<double>(), h->csc_err.as<int>());
+      A = d.as<double>();
     }
-    DevBuf& d = h->own_cin[0];
-    d.ensure(std::max<size_t>(B * m * n, 1) * sizeof(double));
-    if (m) dopt::csc_to_dense(*h, cp, rv ? rv : cp, nz ? nz : d.as<double>(), A_nnz, (int)m, (int)n,
-                              d.as<double>(), h->csc_err.as<int>());
     int herr = 0;
     DOPT_CHECK_HIP(hipMemcpyAsync(&herr, h->csc_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
     DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
     if (herr) throw Error(-1, (herr & 1) ? "CSC colptr is not monotone / out of range"
                                          : "CSC rowval out of range");
-    conic_set_common(h, d.as<double>(), b, c, x, s, y, cone_desc, ncones);
+    conic_set_common(h, A, b, c, x, s, y, cone_desc, ncones);
     return 0;
   });
 }
@@ -1490,15 +1515,8 @@ int dopt_conic_forward(dopt_handle* h, const double* dA, const double* db, const
     if (!out) throw Error(-1, "out is required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    const double* a = stage_in(*h, h->tin[1], dA, B * m * n);
-    const double* b = stage_in(*h, h->tin[2], db, B * m);
-    const double* c = stage_in(*h, h->tin[3], dc, B * n);
-    double* o = out_ptr(*h, h->tout[0], out, B * N);
-    double* ox = out_ptr(*h, h->tout[1], out_dx, B * n);
-    dopt::conic_forward(*h, a, b, c, o, ox);
-    copy_out(*h, out, o, B * N);
-    copy_out(*h, out_dx, ox, B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    conic_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+               [&](const double** i, double** o) { dopt::conic_forward(*h, i[0], i[1], i[2], o[0], o[1]); });
     h->last_time = tm.s();
     return 0;
   });
@@ -1513,24 +1531,12 @@ int dopt_conic_forward_reverse(dopt_handle* h, const double* dA, const double* d
     if (!out || !dx || !out_g) throw Error(-1, "out, dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    const double* a = stage_in(*h, h->tin[1], dA, B * m * n);
-    const double* b = stage_in(*h, h->tin[2], db, B * m);
-    const double* c = stage_in(*h, h->tin[3], dc, B * n);
-    const double* d = stage_in(*h, h->tin[0], dx, B * n);
-    double* o = out_ptr(*h, h->tout[0], out, B * N);
-    double* ox = out_ptr(*h, h->tout[1], out_dx, B * n);
-    double* og = out_ptr(*h, h->tout[2], out_g, B * N);
-    double* oA = out_ptr(*h, h->tout[3], out_dA, B * m * n);
-    double* ob = out_ptr(*h, h->tout[4], out_db, B * m);
-    double* oc = out_ptr(*h, h->tout[5], out_dc, B * n);
-    dopt::conic_forward_reverse(*h, a, b, c, d, o, ox, og, oA, ob, oc);
-    copy_out(*h, out, o, B * N);
-    copy_out(*h, out_dx, ox, B * n);
-    copy_out(*h, out_g, og, B * N);
-    copy_out(*h, out_dA, oA, B * m * n);
-    copy_out(*h, out_db, ob, B * m);
-    copy_out(*h, out_dc, oc, B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    conic_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
+               {{out, 0, B * N}, {out_dx, 1, B * n}, {out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m},
+                {out_dc, 5, B * n}},
+               [&](const double** i, double** o) {
+                 dopt::conic_forward_reverse(*h, i[0], i[1], i[2], i[3], o[0], o[1], o[2], o[3], o[4], o[5]);
+               });
     h->last_time = tm.s();
     return 0;
   });
@@ -1545,6 +1551,7 @@ int dopt_conic_set_maxiter(dopt_handle* h, int32_t maxiter) {
   });
 }
 
+// (what cinfo, cnorm and cinfok hold after each kind of call: the slot table at ConicSeq, conic.hip)
 int dopt_conic_lsqr_stats(dopt_handle* h, int32_t* stats) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_lsqr_stats on a non-conic handle");
@@ -1577,17 +1584,9 @@ int dopt_conic_reverse(dopt_handle* h, const double* dx, double* out_g, double* 
     if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    const double* d = stage_in(*h, h->tin[0], dx, B * n);
-    double* og = out_ptr(*h, h->tout[2], out_g, B * N);
-    double* oA = out_ptr(*h, h->tout[3], out_dA, B * m * n);
-    double* ob = out_ptr(*h, h->tout[4], out_db, B * m);
-    double* oc = out_ptr(*h, h->tout[5], out_dc, B * n);
-    dopt::conic_reverse(*h, d, og, oA, ob, oc);
-    copy_out(*h, out_g, og, B * N);
-    copy_out(*h, out_dA, oA, B * m * n);
-    copy_out(*h, out_db, ob, B * m);
-    copy_out(*h, out_dc, oc, B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    conic_call(*h, 1, {{dx, 0, B * n}},
+               {{out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
+               [&](const double** i, double** o) { dopt::conic_reverse(*h, i[0], o[0], o[1], o[2], o[3]); });
     h->last_time = tm.s();
     return 0;
   });
@@ -1601,18 +1600,10 @@ int dopt_conic_reverse_k(dopt_handle* h, int32_t k, const double* dx, double* ou
     if (k < 1) throw Error(-1, "dopt_conic_reverse_k: k must be at least 1");
     if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
     Timer tm;
-    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1, K = (size_t)k;
-    const double* d = stage_in(*h, h->tin[0], dx, K * B * n);
-    double* og = out_ptr(*h, h->tout[2], out_g, K * B * N);
-    double* oA = out_ptr(*h, h->tout[3], out_dA, K * B * m * n);
-    double* ob = out_ptr(*h, h->tout[4], out_db, K * B * m);
-    double* oc = out_ptr(*h, h->tout[5], out_dc, K * B * n);
-    dopt::conic_reverse_k(*h, k, d, og, oA, ob, oc);
-    copy_out(*h, out_g, og, K * B * N);
-    copy_out(*h, out_dA, oA, K * B * m * n);
-    copy_out(*h, out_db, ob, K * B * m);
-    copy_out(*h, out_dc, oc, K * B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
+    conic_call(*h, k, {{dx, 0, B * n}},
+               {{out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
+               [&](const double** i, double** o) { dopt::conic_reverse_k(*h, k, i[0], o[0], o[1], o[2], o[3]); });
     h->conic_k = k;
     h->last_time = tm.s();
     return 0;
@@ -1627,16 +1618,9 @@ int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const doub
     if (k < 1) throw Error(-1, "dopt_conic_forward_k: k must be at least 1");
     if (!out) throw Error(-1, "out is required");
     Timer tm;
-    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1, K = (size_t)k;
-    const double* a = stage_in(*h, h->tin[1], dA, K * B * m * n);
-    const double* b = stage_in(*h, h->tin[2], db, K * B * m);
-    const double* c = stage_in(*h, h->tin[3], dc, K * B * n);
-    double* o = out_ptr(*h, h->tout[0], out, K * B * N);
-    double* ox = out_ptr(*h, h->tout[1], out_dx, K * B * n);
-    dopt::conic_forward_k(*h, k, a, b, c, o, ox);
-    copy_out(*h, out, o, K * B * N);
-    copy_out(*h, out_dx, ox, K * B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
+    conic_call(*h, k, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+               [&](const double** i, double** o) { dopt::conic_forward_k(*h, k, i[0], i[1], i[2], o[0], o[1]); });
     h->conic_k = k;
     h->last_time = tm.s();
     return 0;

@@ -32,13 +32,6 @@ struct ConeDesc {
   int32_t woff, pad;             // PSD side > PSD_MAX: offset into the global scratch
 };
 
-
-__device__ __forceinline__ int psd_side(int dim) {
-  int d = 0;
-  while ((d + 1) * (d + 2) / 2 <= dim) ++d;
-  return d;
-}
-
 // triangle index (i ≤ j) in MOI column-wise upper-triangle order
 __device__ __forceinline__ int tri_idx(int i, int j) { return j * (j + 1) / 2 + i; }
 
@@ -473,11 +466,11 @@ __device__ __forceinline__ void dpi_apply(const ConeDesc* cones, int ncones, con
     if (cd.code != DOPT_CONE_PSD_TRI) continue;
     const int d = psd_side(cd.dim);
     if (BIG && d > PSD_MAX) {
-      const size_t img = (size_t)((d + 3) & ~3) * (((d + 3) & ~3) + 1);
+      const size_t img = psd_image(d);
       double* g = gws + cd.woff;
       psd_apply_cone(cd, P, in, out, trans, g, g + img, g + 2 * img);
     } else {
-      const size_t img = (size_t)((d + 3) & ~3) * (((d + 3) & ~3) + 1);   // this cone's image: dp × (dp+1)
+      const size_t img = psd_image(d);   // this cone's image: dp × (dp+1)
       // split path: every load of the cone issued up front, the products on
       // 4×4 register tiles (an MFMA form measured no faster, 42 vs 43 µs per
       // dpiU launch at config 5, round 4); the persistent LSQR kernels keep
@@ -688,6 +681,55 @@ struct ConicProblem {
   int m, n;
 };
 
+// The shared opening of the persistent LSQR kernels: the cone table into the
+// workgroup's LDS copy when it fits (returns the table to read from), and
+// problem blockIdx.x's data bound in pr.
+__device__ __forceinline__ const ConeDesc* conic_bind(const ConeDesc* cones_g, int ncones, ConeDesc (&cones_l)[128],
+                                                      const double* A, const double* b, const double* c,
+                                                      const double* v, const double* P, int plen, int m, int n,
+                                                      ConicProblem& pr) {
+  const int bidx = blockIdx.x;
+  const ConeDesc* cn = cones_g;
+  if (ncones <= 128) {
+    for (int k = threadIdx.x; k < ncones; k += CTPB) cones_l[k] = cones_g[k];
+    cn = cones_l;
+  }
+  pr.A = A + (size_t)bidx * m * n;
+  pr.b = b + (size_t)bidx * m;
+  pr.c = c + (size_t)bidx * n;
+  pr.v = v + (size_t)bidx * m;
+  pr.P = P + (size_t)bidx * plen;
+  pr.m = m;
+  pr.n = n;
+  return cn;
+}
+
+// The workspace of one LSQR sequence on the persistent routes, for host and
+// device alike: x, u, vv, w, tmp (N = n + m + 1 each), then the applies'
+// scratch s1, s2, s3 (m each) and s4 (n).  cwork holds one per sequence,
+// sequence q of problem b at block q·B + b (conic_lsqr2_kernel: 2·b + q), and
+// behind all nseq·B of them the right-hand sides, N each, sequence-major.
+struct SeqVec {
+  double *x, *u, *vv, *w, *tmp, *s1, *s2, *s3, *s4;
+  __host__ __device__ static size_t len(size_t N, size_t m, size_t n) { return 5 * N + 3 * m + n; }
+};
+__host__ __device__ __forceinline__ SeqVec seq_vec(double* base, int N, int m) {
+  SeqVec V;
+  V.x = base;
+  V.u = V.x + N;
+  V.vv = V.u + N;
+  V.w = V.vv + N;
+  V.tmp = V.w + N;
+  V.s1 = V.tmp + N;
+  V.s2 = V.s1 + m;
+  V.s3 = V.s2 + m;
+  V.s4 = V.s3 + m;
+  return V;
+}
+__host__ __device__ __forceinline__ double* seq_rhs(double* work, size_t nseq, size_t B, size_t wl) {
+  return work + nseq * B * wl;
+}
+
 // out = M z   (z, out: N = n+m+1; scratch: Dv (m), Au (m), g (n))
 template <class MAT>
 __device__ __forceinline__ void M_apply(const ConicProblem& pr, const MAT& mat, const ConeDesc* cones, int ncones,
@@ -873,29 +915,11 @@ __global__ __launch_bounds__(CTPB) void conic_lsqr_kernel(
   __shared__ double ys[4 * PAIR_ROWS];
   const int bidx = blockIdx.x, t = threadIdx.x;
   const int N = n + m + 1;
-  const ConeDesc* cn = cones_g;
-  if (ncones <= 128) {
-    for (int k = t; k < ncones; k += CTPB) cones[k] = cones_g[k];
-    cn = cones;
-  }
   ConicProblem pr;
-  pr.A = SPARSE ? nullptr : A + (size_t)bidx * m * n;
-  pr.b = b + (size_t)bidx * m;
-  pr.c = c + (size_t)bidx * n;
-  pr.v = v + (size_t)bidx * m;
-  pr.P = P + (size_t)bidx * plen;
-  pr.m = m;
-  pr.n = n;
-  const size_t wl = (size_t)5 * N + 3 * (size_t)m + n;
-  double* x = work + ((size_t)blockIdx.y * gridDim.x + bidx) * wl;
-  double* u = x + N;
-  double* vv = u + N;
-  double* w = vv + N;
-  double* tmp = w + N;
-  double* s1 = tmp + N;   // m
-  double* s2 = s1 + m;    // m
-  double* s3 = s2 + m;    // m
-  double* s4 = s3 + m;    // n
+  const ConeDesc* cn = conic_bind(cones_g, ncones, cones, A, b, c, v, P, plen, m, n, pr);
+  if constexpr (SPARSE) pr.A = nullptr;
+  const size_t wl = SeqVec::len(N, m, n);
+  const SeqVec V = seq_vec(work + ((size_t)blockIdx.y * gridDim.x + bidx) * wl, N, m);
   const double* rb = rhs + (size_t)bidx * N;
   using MAT = typename std::conditional<SPARSE, SparseA<SG>, DenseA>::type;
   MAT mat;
@@ -903,11 +927,11 @@ __global__ __launch_bounds__(CTPB) void conic_lsqr_kernel(
     mat = SparseA<SG>{sa.cp + (size_t)bidx * (n + 1), sa.rp + (size_t)bidx * (m + 1), sa.ri, sa.ci, sa.cv, sa.rv};
   else
     mat = DenseA{pr.A};
-  const ConicM<MAT> op{pr, mat, cn, ncones, s1, s2, s4, lds, red, ys};
+  const ConicM<MAT> op{pr, mat, cn, ncones, V.s1, V.s2, V.s4, lds, red, ys};
   LsqrScalars st;
-  lsqr_solve<CTPB, cblock_sum>(st, op, rb, rhs_zero_tol, maxiter, x, u, vv, w, tmp, N, red);
+  lsqr_solve<CTPB, cblock_sum>(st, op, rb, rhs_zero_tol, maxiter, V.x, V.u, V.vv, V.w, V.tmp, N, red);
   __syncthreads();
-  for (int i = t; i < N; i += CTPB) xout[(size_t)bidx * N + i] = x[i];
+  for (int i = t; i < N; i += CTPB) xout[(size_t)bidx * N + i] = V.x[i];
   if (t == 0 && info) {
     info[bidx] = st.istop;
     info[gridDim.x + bidx] = st.it;
@@ -924,8 +948,7 @@ __global__ __launch_bounds__(CTPB) void conic_lsqr_kernel(
 // stopped, the other continues on the single applies, so both results are
 // bit-identical to two conic_lsqr_kernel runs.
 // ---------------------------------------------------------------------------
-struct LsqrSeq : LsqrScalars {
-  double *x, *u, *vv, *w, *tmp, *s1, *s2, *s4;
+struct LsqrSeq : LsqrScalars, SeqVec {
   const double* rb;
   bool live;
 };
@@ -944,31 +967,13 @@ __global__ __launch_bounds__(CTPB) __attribute__((amdgpu_waves_per_eu(2))) void 
   __shared__ double ys[2 * 4 * PAIR_ROWS];
   const int bidx = blockIdx.x, t = threadIdx.x;
   const int N = n + m + 1;
-  const ConeDesc* cn = cones_g;
-  if (ncones <= 128) {
-    for (int k = t; k < ncones; k += CTPB) cones[k] = cones_g[k];
-    cn = cones;
-  }
   ConicProblem pr;
-  pr.A = A + (size_t)bidx * m * n;
-  pr.b = b + (size_t)bidx * m;
-  pr.c = c + (size_t)bidx * n;
-  pr.v = v + (size_t)bidx * m;
-  pr.P = P + (size_t)bidx * plen;
-  pr.m = m;
-  pr.n = n;
-  const size_t wl = (size_t)5 * N + 3 * (size_t)m + n;
+  const ConeDesc* cn = conic_bind(cones_g, ncones, cones, A, b, c, v, P, plen, m, n, pr);
+  const size_t wl = SeqVec::len(N, m, n);
   LsqrSeq S[2] = {};
   for (int q = 0; q < 2; ++q) {
     LsqrSeq& Q = S[q];
-    Q.x = work + ((size_t)2 * bidx + q) * wl;
-    Q.u = Q.x + N;
-    Q.vv = Q.u + N;
-    Q.w = Q.vv + N;
-    Q.tmp = Q.w + N;
-    Q.s1 = Q.tmp + N;
-    Q.s2 = Q.s1 + m;
-    Q.s4 = Q.s2 + 2 * (size_t)m;
+    static_cast<SeqVec&>(Q) = seq_vec(work + ((size_t)2 * bidx + q) * wl, N, m);
     Q.rb = (q == 0 ? rhs_f : rhs_r) + (size_t)bidx * N;
     Q.beta = sqrt(lsqr_load_rhs<CTPB, cblock_sum>(Q.rb, Q.u, Q.x, N, red));
   }
@@ -1089,22 +1094,6 @@ struct SeqState : LsqrScalars {
     (D).rnorm = (S_).rnorm; (D).arnorm = (S_).arnorm; (D).xnorm = (S_).xnorm;                             \
     (D).it = (S_).it; (D).istop = (S_).istop; (D).live = (S_).live; (D).mt = (S_).mt;                     \
   } while (0)
-
-struct SeqVec {
-  double *x, *u, *vv, *w, *tmp, *s1, *s2, *s4;
-};
-__device__ __forceinline__ SeqVec seq_vec(double* base, int N, int m) {
-  SeqVec V;
-  V.x = base;
-  V.u = V.x + N;
-  V.vv = V.u + N;
-  V.w = V.vv + N;
-  V.tmp = V.w + N;
-  V.s1 = V.tmp + N;
-  V.s2 = V.s1 + m;
-  V.s4 = V.s2 + 2 * (size_t)m;
-  return V;
-}
 
 __device__ __forceinline__ int uniform(int v) { return __builtin_amdgcn_readfirstlane(v); }
 
@@ -1236,20 +1225,9 @@ __global__ __launch_bounds__(CTPB) void conic_lsqrk_kernel(
   const int seed0 = blockIdx.y * G;
   const int ng = min(G, k - seed0);   // this group's sequences: seeds seed0 … seed0 + ng − 1
   const int N = n + m + 1;
-  const ConeDesc* cn = cones_g;
-  if (ncones <= 128) {
-    for (int q = t; q < ncones; q += CTPB) cones[q] = cones_g[q];
-    cn = cones;
-  }
   ConicProblem pr;
-  pr.A = A + (size_t)bidx * m * n;
-  pr.b = b + (size_t)bidx * m;
-  pr.c = c + (size_t)bidx * n;
-  pr.v = v + (size_t)bidx * m;
-  pr.P = P + (size_t)bidx * plen;
-  pr.m = m;
-  pr.n = n;
-  const size_t wl = (size_t)5 * N + 3 * (size_t)m + n;
+  const ConeDesc* cn = conic_bind(cones_g, ncones, cones, A, b, c, v, P, plen, m, n, pr);
+  const size_t wl = SeqVec::len(N, m, n);
   const size_t qs = (size_t)B * wl;                          // workspace stride between seeds
   double* wb0 = work + ((size_t)seed0 * B + bidx) * wl;      // sequence q of the group: wb0 + q·qs
   for (int q = 0; q < ng; ++q) {
@@ -2278,11 +2256,8 @@ static size_t dpi_lds_bytes(const std::vector<int32_t>& cones) {
   size_t best = 16;
   for (size_t k = 0; k < cones.size() / 2; ++k)
     if (cones[2 * k] == DOPT_CONE_PSD_TRI) {
-      int d = 0;
-      while ((d + 1) * (d + 2) / 2 <= cones[2 * k + 1]) ++d;
-      if (d > PSD_MAX) continue;
-      const size_t dp = (size_t)((d + 3) & ~3);
-      best = std::max(best, 3 * dp * (dp + 1) * sizeof(double));
+      const int d = psd_side(cones[2 * k + 1]);
+      if (d <= PSD_MAX) best = std::max(best, psd_image_len(d) * sizeof(double));
     }
   return best;
 }
@@ -2300,13 +2275,11 @@ void conic_factor(Handle& h) {
     if (code == DOPT_CONE_NONNEG || code == DOPT_CONE_NONPOS) poff += dim;
     else if (code == DOPT_CONE_SOC) poff += 4;
     else if (code == DOPT_CONE_PSD_TRI) {
-      int d = 0;
-      while ((d + 1) * (d + 2) / 2 <= dim) ++d;
+      const int d = psd_side(dim);
       poff += 2 * d * d + 2;
       if (d > PSD_MAX) {   // global scratch: 3 apply images (≥ the eigensolver's X and V)
-        const int dp = (d + 3) & ~3;
         cd[k].woff = woff;
-        woff += 3 * dp * (dp + 1);
+        woff += (int)psd_image_len(d);
       }
     }
   }
@@ -2351,8 +2324,61 @@ static int lsqr_maxiter(const Handle& h) {
   return h.lsqr_cap > 0 && h.lsqr_cap < N ? h.lsqr_cap : N;
 }
 
-// Split-path LSQR (see conic_split_* above) of nq sequences per problem
-// (rhs: nq·B right-hand sides, sequence q·B + b), co-iterated for nq = 2.
+// ---------------------------------------------------------------------------
+// A conic call is a table of LSQR sequences (ConicSeq), run by conic_run.  A
+// sequence's direction fixes its right-hand-side kernel, its zero test on
+// ‖rhs‖ and its output kernel; its slot says where the run's
+// [istop | iterations] and its four norms (rnorm, arnorm, xnorm, anorm) go:
+//   SLOT_LAST      cinfo [0, 2B),  cnorm [0, 4B)   a single call's run and the
+//                  reverse run of forward_reverse: what dopt_get_info and
+//                  dopt_get_system_size report, the front of
+//                  dopt_conic_lsqr_stats / dopt_conic_lsqr_norms
+//   SLOT_FWD       cinfo [2B, 4B), cnorm [4B, 8B)  the forward run of
+//                  forward_reverse: the back of those two getters (a single
+//                  call leaves it as it was)
+//   SLOT_SEED0 + j cinfok [2B·j, 2B·(j+1))          seed j of a _k call
+//                  (dopt_conic_lsqr_stats_k); seed 0's norms go to cnorm
+//                  [0, 4B), and after the call SLOT_LAST holds seed 0's block
+// ---------------------------------------------------------------------------
+enum ConicDir { CONIC_FWD = 0, CONIC_REV = 1 };
+enum { SLOT_LAST = 0, SLOT_FWD = 1, SLOT_SEED0 = 2 };
+struct ConicSeq {
+  ConicDir dir;
+  const double *dA, *db, *dc;   // forward: the tangents (each may be null)
+  const double* dx;             // reverse: the seed
+  double* sol;                  // LSQR's solution, N per problem: forward's out, reverse's g
+  double* out_dx;               // forward: ForwardVariablePrimal (null: not wanted)
+  double *out_dA, *out_db, *out_dc;   // reverse: the gradients (null: not wanted)
+  int slot;
+  // filled by conic_run:
+  double* rhs;         // this sequence's B right-hand sides in cwork
+  int32_t* info;
+  double* norms;       // (null: not kept)
+};
+static ConicSeq fwd_seq(const double* dA, const double* db, const double* dc, double* out, double* out_dx,
+                        int slot) {
+  ConicSeq q = {};
+  q.dir = CONIC_FWD, q.dA = dA, q.db = db, q.dc = dc, q.sol = out, q.out_dx = out_dx, q.slot = slot;
+  return q;
+}
+static ConicSeq rev_seq(const double* dx, double* out_g, double* out_dA, double* out_db, double* out_dc,
+                        int slot) {
+  ConicSeq q = {};
+  q.dir = CONIC_REV, q.dx = dx, q.sol = out_g, q.slot = slot;
+  q.out_dA = out_dA, q.out_db = out_db, q.out_dc = out_dc;
+  return q;
+}
+// LSQR returns 0 without iterating for ‖rhs‖ ≤ tol.  Forward: `norm(RHS) <=
+// 1e-400` ≡ RHS == 0 (ConicProgram.jl:320); reverse: `norm(dz) <= 1e-4` → g = 0
+// (ConicProgram.jl:369-370)
+static double seq_tol(const ConicSeq& q) { return q.dir == CONIC_FWD ? 0.0 : 1e-4; }
+static bool seq_has_output(const ConicSeq& q) {
+  return q.dir == CONIC_FWD ? q.out_dx != nullptr : q.out_dA || q.out_db || q.out_dc;
+}
+
+// Split-path LSQR (see conic_split_* above) of the nq (1 or 2) sequences of
+// `seq` per problem (their nq·B right-hand sides from seq[0].rhs on, sequence
+// q·B + b), co-iterated for nq = 2.
 //
 // Batch slices (round 5): the fused form runs the batch
 // as two halves, each with its own workspace, on the handle's stream and on
@@ -2362,8 +2388,9 @@ static int lsqr_maxiter(const Handle& h) {
 // instead of leaving it idle between them.  Every sequence's arithmetic is
 // unchanged (a half is the same kernels over fewer problems), so the results
 // are bit-identical to one slice.
-static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const double* rhs, double* out0,
-                             int32_t* info0, double* out1, int32_t* info1, double* norms0, double* norms1) {
+static void conic_lsqr_split(Handle& h, const ConicSeq* seq, int nq) {
+  const ConicSeq& q0 = seq[0];
+  const ConicSeq q1 = nq > 1 ? seq[1] : ConicSeq{};   // (one sequence: no second set of outputs)
   const int B = (int)h.batch, m = h.m, n = h.n;
   const int maxit = lsqr_maxiter(h);
   const int nc = (int)h.cones.size() / 2;
@@ -2374,21 +2401,7 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
   const bool fuse = h.split_fuse && nc > 0 && n <= SPLIT_FUSE_NMAX;
   const int ns = fuse && B >= 2 ? 2 : 1;   // batch slices
   const int PL = 3 * RB + 3 * nc + 4 * CTPB;
-  const size_t per = fuse ? (size_t)6 * N + 3 * M1 + (size_t)2 * RB * n + PL + n
-                          : (size_t)5 * N + 4 * M1 + (size_t)RB * n;
-  // one region per slice: vectors, then 2·V_s states, then the active counter
   const int Bs0 = (B + ns - 1) / ns;
-  const size_t region = (((size_t)nq * Bs0 * per * sizeof(double) + (size_t)2 * nq * Bs0 * sizeof(LsqrState) + 64) +
-                         255) & ~(size_t)255;
-  h.csplit.ensure(ns * region);
-  h.psd_app.ensure(std::max<size_t>((size_t)nq * B * h.psd_big_len, 1) * sizeof(double));
-  const size_t dl = dpi_lds_bytes(h.cones);
-  const ConeDesc* cd = h.cone_dev.as<ConeDesc>();
-  if (ns > 1) {
-    ensure_aux(h);
-    DOPT_CHECK_HIP(hipEventRecord(h.ev_fork, h.stream));   // aux after everything queued before the LSQR
-    DOPT_CHECK_HIP(hipStreamWaitEvent(h.aux, h.ev_fork, 0));
-  }
   struct Slice {
     int b0, Bs, V, par, left;
     hipStream_t st;
@@ -2399,6 +2412,45 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
     const double *A, *bv, *cv, *vcone, *P;
     double* gws;
   } sl[2];
+  // One slice's region (S.V sequences), bump-carved from `base`: each `vec`
+  // hands out S.V blocks of `count` doubles and advances; the 2·V states and
+  // the active counter's 64 bytes follow the vectors.  Where the carve ends is
+  // the region's size, so the two cannot disagree; base = nullptr measures.
+  auto carve = [&](Slice& S, char* base) {
+    size_t off = 0;
+    auto bump = [&](size_t bytes) {
+      char* p = base ? base + off : nullptr;
+      off += bytes;
+      return p;
+    };
+    auto vec = [&](size_t count) { return reinterpret_cast<double*>(bump(S.V * count * sizeof(double))); };
+    SplitWS& ws = S.ws;
+    FSplit& fs = S.fs;
+    const size_t gp = (size_t)RB * n;   // one sequence's partial Aᵀ products
+    if (fuse) {
+      fs.x = vec(N), fs.w = vec(N), fs.u0 = vec(N), fs.u1 = vec(N), fs.v0 = vec(N), fs.v1 = vec(N);
+      fs.Dv = vec(M1), fs.tmpm = vec(M1), fs.yb = vec(M1);
+      fs.gpM = vec(gp), fs.gpT = vec(gp), fs.part = vec(PL), fs.ut = vec(n);
+    } else {
+      ws.x = vec(N), ws.u = vec(N), ws.v = vec(N), ws.w = vec(N), ws.out = vec(N);
+      ws.Dv = vec(M1), ws.tmpm = vec(M1), ws.yb = vec(M1);
+      ws.gpart = vec(gp);
+    }
+    S.stv = reinterpret_cast<LsqrState*>(bump((size_t)2 * S.V * sizeof(LsqrState)));
+    S.active = reinterpret_cast<int32_t*>(bump(64));
+    return off;
+  };
+  sl[0].V = nq * Bs0;   // the larger slice sizes the regions
+  const size_t region = (carve(sl[0], nullptr) + 255) & ~(size_t)255;
+  h.csplit.ensure(ns * region);
+  h.psd_app.ensure(std::max<size_t>((size_t)nq * B * h.psd_big_len, 1) * sizeof(double));
+  const size_t dl = dpi_lds_bytes(h.cones);
+  const ConeDesc* cd = h.cone_dev.as<ConeDesc>();
+  if (ns > 1) {
+    ensure_aux(h);
+    DOPT_CHECK_HIP(hipEventRecord(h.ev_fork, h.stream));   // aux after everything queued before the LSQR
+    DOPT_CHECK_HIP(hipStreamWaitEvent(h.aux, h.ev_fork, 0));
+  }
   for (int s = 0; s < ns; ++s) {
     Slice& S = sl[s];
     S.b0 = s * Bs0;
@@ -2407,27 +2459,12 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
     S.par = 0;
     S.left = S.V;
     S.st = s ? h.aux : h.stream;
-    char* rbase = reinterpret_cast<char*>(h.csplit.p) + s * region;
-    double* base = reinterpret_cast<double*>(rbase);
-    const int V = S.V;
+    carve(S, reinterpret_cast<char*>(h.csplit.p) + s * region);
     SplitWS& ws = S.ws;
     FSplit& fs = S.fs;
     if (fuse) {
-      fs.x = base;
-      fs.w = fs.x + (size_t)V * N;
-      fs.u0 = fs.w + (size_t)V * N;
-      fs.u1 = fs.u0 + (size_t)V * N;
-      fs.v0 = fs.u1 + (size_t)V * N;
-      fs.v1 = fs.v0 + (size_t)V * N;
-      fs.Dv = fs.v1 + (size_t)V * N;
-      fs.tmpm = fs.Dv + (size_t)V * M1;
-      fs.yb = fs.tmpm + (size_t)V * M1;
-      fs.gpM = fs.yb + (size_t)V * M1;
-      fs.gpT = fs.gpM + (size_t)V * RB * n;
-      fs.part = fs.gpT + (size_t)V * RB * n;
-      fs.ut = fs.part + (size_t)V * PL;
-      fs.s0 = reinterpret_cast<LsqrState*>(base + (size_t)V * per);
-      fs.s1 = fs.s0 + V;
+      fs.s0 = S.stv;
+      fs.s1 = fs.s0 + S.V;
       fs.N = N;
       fs.m = m;
       fs.n = n;
@@ -2446,25 +2483,12 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
       ws.tmpm = fs.tmpm;
       ws.yb = fs.yb;
       ws.gpart = fs.gpT;
-      S.stv = fs.s0;
-    } else {
-      ws.x = base;
-      ws.u = ws.x + (size_t)V * N;
-      ws.v = ws.u + (size_t)V * N;
-      ws.w = ws.v + (size_t)V * N;
-      ws.out = ws.w + (size_t)V * N;
-      ws.Dv = ws.out + (size_t)V * N;
-      ws.tmpm = ws.Dv + (size_t)V * M1;
-      ws.yb = ws.tmpm + (size_t)V * M1;
-      ws.gpart = ws.yb + (size_t)V * M1;
-      S.stv = reinterpret_cast<LsqrState*>(base + (size_t)V * per);
     }
     ws.N = N;
     ws.m = m;
     ws.n = n;
     ws.RB = RB;
     ws.B = S.Bs;
-    S.active = reinterpret_cast<int32_t*>(reinterpret_cast<LsqrState*>(base + (size_t)V * per) + 2 * V);
     S.A = h.cA + (size_t)S.b0 * m * n;
     S.bv = h.cb + (size_t)S.b0 * m;
     S.cv = h.cc + (size_t)S.b0 * n;
@@ -2487,8 +2511,8 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
     Slice& S = sl[s];
     const int32_t nact = S.V;
     DOPT_CHECK_HIP(hipMemcpyAsync(S.active, &nact, sizeof(int32_t), hipMemcpyHostToDevice, S.st));
-    hipLaunchKernelGGL(conic_split_init_kernel, dim3(S.V), dim3(CTPB), 0, S.st, rhs, (size_t)B * N, S.b0, tol0,
-                       tol1, S.ws, S.stv, S.active);
+    hipLaunchKernelGGL(conic_split_init_kernel, dim3(S.V), dim3(CTPB), 0, S.st, q0.rhs, (size_t)B * N, S.b0,
+                       seq_tol(q0), seq_tol(seq[nq - 1]), S.ws, S.stv, S.active);
     passT(S);
     hipLaunchKernelGGL(conic_split_init2_kernel, dim3(S.V), dim3(VT), 0, S.st, S.bv, S.cv, S.ws, S.stv, S.active,
                        fuse ? S.fs.part + 3 * RB + nc : nullptr, PL, nc);
@@ -2563,10 +2587,10 @@ static void conic_lsqr_split(Handle& h, int nq, double tol0, double tol1, const 
   for (int s = 0; s < ns; ++s) {
     Slice& S = sl[s];
     hipLaunchKernelGGL(conic_split_out_kernel, dim3(S.V), dim3(CTPB), 0, S.st, S.ws,
-                       fuse ? (S.par ? S.fs.s1 : S.fs.s0) : S.stv, out0 + (size_t)S.b0 * N,
-                       info0 ? info0 + S.b0 : nullptr, out1 ? out1 + (size_t)S.b0 * N : nullptr,
-                       info1 ? info1 + S.b0 : nullptr, norms0 ? norms0 + (size_t)4 * S.b0 : nullptr,
-                       norms1 ? norms1 + (size_t)4 * S.b0 : nullptr, B);
+                       fuse ? (S.par ? S.fs.s1 : S.fs.s0) : S.stv, q0.sol + (size_t)S.b0 * N,
+                       q0.info ? q0.info + S.b0 : nullptr, q1.sol ? q1.sol + (size_t)S.b0 * N : nullptr,
+                       q1.info ? q1.info + S.b0 : nullptr, q0.norms ? q0.norms + (size_t)4 * S.b0 : nullptr,
+                       q1.norms ? q1.norms + (size_t)4 * S.b0 : nullptr, B);
   }
   if (ns > 1) {   // the handle's stream continues after both slices
     DOPT_CHECK_HIP(hipEventRecord(h.ev_join, h.aux));
@@ -2588,22 +2612,20 @@ static SpConic sp_conic(const Handle& h) {
                  st.rv.as<double>()};
 }
 
-// nq (1 or 2) persistent LSQR sequences per problem on the sparse A_moi, side
-// by side in one launch (rhs, out: N per problem; info / norms at the given
-// offsets).  The caller sized cwork: nq·B·wl of workspace at its front, the
-// right-hand sides behind it.
-static void conic_lsqr_sparse(Handle& h, int nq, double tol, const double* rhs, double* out, int32_t* info,
-                              double* norms, double tol2 = 0.0, const double* rhs2 = nullptr, double* out2 = nullptr,
-                              int32_t* info2 = nullptr, double* norms2 = nullptr) {
+// The nq (1 or 2) sequences of `seq` per problem as persistent LSQR runs on
+// the sparse A_moi, side by side in one launch.
+static void conic_lsqr_sparse(Handle& h, const ConicSeq* seq, int nq) {
+  const ConicSeq& q0 = seq[0];
+  const ConicSeq q1 = nq > 1 ? seq[1] : ConicSeq{};   // (one sequence: gridDim.y = 1 never reads the second set)
   const int B = (int)h.batch, m = h.m, n = h.n;
   const int nc = (int)h.cones.size() / 2;
   const int G = sp_lanes(2.0 * (double)h.sp[0].nnz / std::max<double>(1.0, (double)B * (m + n)));
   PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
   auto go = [&](auto kern) {
     hipLaunchKernelGGL(kern, dim3(B, nq), dim3(CTPB), dpi_lds_bytes(h.cones), h.stream, h.cone_dev.as<ConeDesc>(),
-                       nc, nullptr, h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(), h.dpi_len, m, n, rhs, tol,
-                       h.cwork.as<double>(), out, info, norms, lsqr_maxiter(h), sp_conic(h), rhs2, tol2, out2, info2,
-                       norms2);
+                       nc, nullptr, h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(), h.dpi_len, m, n, q0.rhs,
+                       seq_tol(q0), h.cwork.as<double>(), q0.sol, q0.info, q0.norms, lsqr_maxiter(h), sp_conic(h),
+                       q1.rhs, seq_tol(q1), q1.sol, q1.info, q1.norms);
   };
   if (G == 1) go(conic_lsqr_kernel<true, 1>);
   else if (G == 4) go(conic_lsqr_kernel<true, 4>);
@@ -2611,153 +2633,39 @@ static void conic_lsqr_sparse(Handle& h, int nq, double tol, const double* rhs, 
   check_launch();
 }
 
-static void conic_lsqr(Handle& h, double tol, double* out) {
+// One dense sequence per problem: conic_lsqr_kernel<false>
+static void conic_lsqr_one(Handle& h, const ConicSeq& q) {
   const int B = (int)h.batch, m = h.m, n = h.n;
   const int nc = (int)h.cones.size() / 2;
-  const size_t N = (size_t)n + m + 1;
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)B * (wl + N) * sizeof(double));
-  h.cinfo.ensure((size_t)4 * std::max(B, 1) * sizeof(int32_t));
-  h.cnorm.ensure((size_t)8 * std::max(B, 1) * sizeof(double));
-  double* rhs = h.cwork.as<double>() + (size_t)B * wl;
-  if (h.sparse) {
-    conic_lsqr_sparse(h, 1, tol, rhs, out, h.cinfo.as<int32_t>(), h.cnorm.as<double>());
-    return;
-  }
-  if (use_split(h)) {
-    conic_lsqr_split(h, 1, tol, tol, rhs, out, h.cinfo.as<int32_t>(), nullptr, nullptr, h.cnorm.as<double>(),
-                     nullptr);
-    return;
-  }
   PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
   hipLaunchKernelGGL(conic_lsqr_kernel<false>, dim3(B), dim3(CTPB), dpi_lds_bytes(h.cones), h.stream,
                      h.cone_dev.as<ConeDesc>(), nc, h.cA, h.cb, h.cc, h.vp.as<double>(),
-                     h.dpi.as<double>(), h.dpi_len, m, n, rhs, tol, h.cwork.as<double>(), out,
-                     h.cinfo.as<int32_t>(), h.cnorm.as<double>(), lsqr_maxiter(h), SpConic{}, nullptr, 0.0, nullptr,
-                     nullptr, nullptr);
+                     h.dpi.as<double>(), h.dpi_len, m, n, q.rhs, seq_tol(q), h.cwork.as<double>(), q.sol, q.info,
+                     q.norms, lsqr_maxiter(h), SpConic{}, nullptr, 0.0, nullptr, nullptr, nullptr);
   check_launch();
 }
 
-void conic_forward(Handle& h, const double* dA, const double* db, const double* dc,
-                   double* out, double* out_dx) {
-  if (!h.cfactored) conic_factor(h);
+// A forward and a reverse sequence per problem, co-iterated: one sweep over A
+// per M / Mᵀ apply for both directions (conic_lsqr2_kernel)
+static void conic_lsqr_pair(Handle& h, const ConicSeq& f, const ConicSeq& r) {
   const int B = (int)h.batch, m = h.m, n = h.n;
-  const size_t N = (size_t)n + m + 1;
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)B * (wl + N) * sizeof(double));
-  double* rhs = h.cwork.as<double>() + (size_t)B * wl;
-  {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
-    hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA, db, dc, h.cx,
-                       h.vp.as<double>() + (size_t)B * m, m, n, rhs);
-    check_launch();
-  }
-  conic_lsqr(h, 0.0, out);   // `norm(RHS) <= 1e-400` ≡ RHS == 0 (ConicProgram.jl:320)
-  if (out_dx) {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
-    hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out, h.cx, m, n, out_dx);
-    check_launch();
-  }
-}
-
-void conic_reverse(Handle& h, const double* dx, double* out_g, double* out_dA, double* out_db,
-                   double* out_dc) {
-  if (!h.cfactored) conic_factor(h);
-  const int B = (int)h.batch, m = h.m, n = h.n;
-  const size_t N = (size_t)n + m + 1;
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)B * (wl + N) * sizeof(double));
-  double* rhs = h.cwork.as<double>() + (size_t)B * wl;
-  {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
-    hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx, h.cx, m, n, rhs);
-    check_launch();
-  }
-  conic_lsqr(h, 1e-4, out_g);  // `norm(dz) <= 1e-4` → g = 0 (ConicProgram.jl:369-370)
-  if (out_dA || out_db || out_dc) {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
-    hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g, h.cx,
-                       h.vp.as<double>() + (size_t)B * m, m, n, out_dA, out_db, out_dc);
-    check_launch();
-  }
-}
-
-// Forward and reverse of every problem in one call: both right-hand sides,
-// then the co-iterated LSQR (conic_lsqr2_kernel, or the split path with two
-// sequences per problem for m > 2·PAIR_ROWS: one sweep over A per M / Mᵀ
-// apply for both directions), then both output kernels.  Results are
-// bit-identical to conic_forward + conic_reverse.  Info: the reverse run's
-// [istop | iterations] where a single call leaves them (dopt_get_info), the
-// forward run's behind it (dopt_conic_lsqr_stats).
-void conic_forward_reverse(Handle& h, const double* dA, const double* db, const double* dc, const double* dx,
-                           double* out_f, double* out_dx, double* out_g, double* out_dA, double* out_db,
-                           double* out_dc) {
-  if (!h.cfactored) conic_factor(h);
-  const int B = (int)h.batch, m = h.m, n = h.n;
-  h.cinfo.ensure((size_t)4 * std::max(B, 1) * sizeof(int32_t));
-  h.cnorm.ensure((size_t)8 * std::max(B, 1) * sizeof(double));
-  double* nrm = h.cnorm.as<double>();
   const int nc = (int)h.cones.size() / 2;
-  const size_t N = (size_t)n + m + 1;
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)B * (2 * wl + 2 * N) * sizeof(double));
-  double* rhs_f = h.cwork.as<double>() + (size_t)B * 2 * wl;
-  double* rhs_r = rhs_f + (size_t)B * N;
-  {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
-    hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA, db, dc, h.cx,
-                       h.vp.as<double>() + (size_t)B * m, m, n, rhs_f);
-    hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx, h.cx, m, n, rhs_r);
-    check_launch();
-  }
-  if (h.sparse) {   // the two sequences side by side in one launch (each equal to its separate call)
-    int32_t* info = h.cinfo.as<int32_t>();
-    conic_lsqr_sparse(h, 2, 0.0, rhs_f, out_f, info + 2 * B, nrm + 4 * (size_t)B, 1e-4, rhs_r, out_g, info, nrm);
-  } else if (use_split(h)) {
-    int32_t* info = h.cinfo.as<int32_t>();
-    conic_lsqr_split(h, 2, 0.0, 1e-4, rhs_f, out_f, info + 2 * B, out_g, info, nrm + 4 * (size_t)B, nrm);
-  } else {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
-    int32_t* info = h.cinfo.as<int32_t>();
-    hipLaunchKernelGGL(conic_lsqr2_kernel, dim3(B), dim3(CTPB), dpi_lds_bytes(h.cones), h.stream,
-                       h.cone_dev.as<ConeDesc>(), nc, h.cA, h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(),
-                       h.dpi_len, m, n, rhs_f, 0.0, rhs_r, 1e-4, h.cwork.as<double>(), out_f, out_g,
-                       info + 2 * B, info, nrm + 4 * (size_t)B, nrm, lsqr_maxiter(h));
-    check_launch();
-  }
-  PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
-  if (out_dx)
-    hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_f, h.cx, m, n, out_dx);
-  if (out_dA || out_db || out_dc)
-    hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g, h.cx,
-                       h.vp.as<double>() + (size_t)B * m, m, n, out_dA, out_db, out_dc);
+  PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
+  hipLaunchKernelGGL(conic_lsqr2_kernel, dim3(B), dim3(CTPB), dpi_lds_bytes(h.cones), h.stream,
+                     h.cone_dev.as<ConeDesc>(), nc, h.cA, h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(),
+                     h.dpi_len, m, n, f.rhs, seq_tol(f), r.rhs, seq_tol(r), h.cwork.as<double>(), f.sol, r.sol,
+                     f.info, r.info, f.norms, r.norms, lsqr_maxiter(h));
   check_launch();
 }
 
-// ---------------------------------------------------------------------------
-// k seeds per problem (dopt_conic_reverse_k / dopt_conic_forward_k), seed-major:
-// seed j's vectors are the batch block at j·B·len.  Dense persistent route:
-// all k right-hand sides, one conic_lsqrk_kernel launch (groups of LSQRK_G
-// seeds per workgroup sharing each sweep over A), the outputs per seed.  Split
-// and sparse routes, and k = 1: the single-seed call per seed (no shared sweep
-// there yet).  Per-seed [istop | iterations] in cinfok; the single-call info and
-// norms (cinfo, cnorm) end as seed 0's.
-// ---------------------------------------------------------------------------
-// (one seed: the single-sequence kernel, two workgroups per CU where the group kernel's registers allow one)
-static bool multi_shared_sweep(const Handle& h, int k) { return k > 1 && !h.sparse && !use_split(h); }
-
-static void keep_seed_info(Handle& h, int j) {
-  const size_t B = h.batch;
-  DOPT_CHECK_HIP(hipMemcpyAsync(h.cinfok.as<int32_t>() + (size_t)j * 2 * B, h.cinfo.p, 2 * B * sizeof(int32_t),
-                                hipMemcpyDeviceToDevice, h.stream));
-}
-
-// rhs: k·B right-hand sides behind the k·B workspaces of cwork (sized by the caller)
-static void conic_lsqr_k(Handle& h, int k, double tol, const double* rhs, double* out) {
+// k > 1 same-direction seeds per problem on the dense persistent route: one
+// conic_lsqrk_kernel launch, groups of LSQRK_G seeds per workgroup sharing each
+// sweep over A.  The seeds' right-hand sides, solutions and cinfok blocks are
+// consecutive from seed 0's on (seed j: batch block j).
+static void conic_lsqr_seeds(Handle& h, const ConicSeq* seq, int k) {
+  const ConicSeq& q0 = seq[0];
   const int B = (int)h.batch, m = h.m, n = h.n;
   const int nc = (int)h.cones.size() / 2;
-  h.cinfo.ensure((size_t)4 * std::max(B, 1) * sizeof(int32_t));
-  h.cnorm.ensure((size_t)8 * std::max(B, 1) * sizeof(double));
   const size_t dl = dpi_lds_bytes(h.cones);
   // static LDS of conic_lsqrk_kernel<G>: ys (G·4·PAIR_ROWS doubles), the cone table, the states and lists
   auto fits = [&](int G) {
@@ -2767,87 +2675,145 @@ static void conic_lsqr_k(Handle& h, int k, double tol, const double* rhs, double
   PhaseTimer pt(h, DOPT_PHASE_CONIC_LSQR);
   auto go = [&](auto kern, int G) {
     hipLaunchKernelGGL(kern, dim3(B, (k + G - 1) / G), dim3(CTPB), dl, h.stream, h.cone_dev.as<ConeDesc>(), nc, h.cA,
-                       h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(), h.dpi_len, m, n, k, rhs, tol,
-                       h.cwork.as<double>(), out, h.cinfok.as<int32_t>(), h.cnorm.as<double>(), lsqr_maxiter(h));
+                       h.cb, h.cc, h.vp.as<double>(), h.dpi.as<double>(), h.dpi_len, m, n, k, q0.rhs, seq_tol(q0),
+                       h.cwork.as<double>(), q0.sol, q0.info, q0.norms, lsqr_maxiter(h));
   };
   if (fits(LSQRK_G)) go(conic_lsqrk_kernel<LSQRK_G>, LSQRK_G);
   else go(conic_lsqrk_kernel<2>, 2);   // PSD sides near PSD_MAX: their Dπ images leave LDS for two sequences' ys
   check_launch();
-  // seed 0's [istop | iterations] where a single call leaves them (its norms: written there by the kernel)
-  DOPT_CHECK_HIP(hipMemcpyAsync(h.cinfo.p, h.cinfok.p, (size_t)2 * B * sizeof(int32_t), hipMemcpyDeviceToDevice,
-                                h.stream));
 }
+
+// one slot's [istop | iterations] block into another slot
+static void copy_seed_info(Handle& h, int32_t* dst, const int32_t* src) {
+  DOPT_CHECK_HIP(hipMemcpyAsync(dst, src, 2 * h.batch * sizeof(int32_t), hipMemcpyDeviceToDevice, h.stream));
+}
+
+// Runs the call `seq` describes: one sequence; a forward and a reverse one
+// (forward first; each result bit-identical to its single call); or k seeds
+// of one direction (slots SLOT_SEED0 + j, vectors seed-major: seed j's are the
+// batch block at j·B·len).  Routes:
+//   sparse handle        conic_lsqr_kernel<true, G>, one or two sequences per launch
+//   use_split            conic_lsqr_split, one or two sequences
+//   one dense sequence   conic_lsqr_kernel<false>
+//   forward + reverse    conic_lsqr2_kernel
+//   k > 1 seeds          conic_lsqrk_kernel<4> or <2>; on the sparse and split
+//                        routes, and for k = 1, the single-sequence call per
+//                        seed (no shared sweep there yet; one seed: two
+//                        workgroups per CU where the group kernel's registers
+//                        allow one)
+static void conic_run(Handle& h, ConicSeq* seq, int nseq) {
+  if (!h.cfactored) conic_factor(h);
+  const int B = (int)h.batch, m = h.m, n = h.n;
+  const size_t Bz = h.batch, N = (size_t)n + m + 1;
+  const bool seeds = seq[0].slot >= SLOT_SEED0;
+  if (seeds) {
+    h.cinfok.ensure((size_t)2 * std::max(B, 1) * nseq * sizeof(int32_t));
+    if (nseq == 1 || h.sparse || use_split(h)) {
+      for (int j = nseq - 1; j >= 0; --j) {   // seed 0 last: the single-call info and norms end as its
+        ConicSeq one = seq[j];
+        one.slot = SLOT_LAST;
+        conic_run(h, &one, 1);
+        copy_seed_info(h, h.cinfok.as<int32_t>() + (size_t)j * 2 * Bz, one.info);
+      }
+      return;
+    }
+  }
+  const size_t wl = SeqVec::len(N, m, n);
+  h.cwork.ensure(nseq * Bz * (wl + N) * sizeof(double));
+  h.cinfo.ensure((size_t)4 * std::max(B, 1) * sizeof(int32_t));
+  h.cnorm.ensure((size_t)8 * std::max(B, 1) * sizeof(double));
+  const double* vp = h.vp.as<double>() + Bz * m;
+  for (int q = 0; q < nseq; ++q) {
+    ConicSeq& s = seq[q];
+    s.rhs = seq_rhs(h.cwork.as<double>(), nseq, Bz, wl) + q * Bz * N;
+    if (seeds) {
+      s.info = h.cinfok.as<int32_t>() + (size_t)(s.slot - SLOT_SEED0) * 2 * Bz;
+      s.norms = s.slot == SLOT_SEED0 ? h.cnorm.as<double>() : nullptr;
+    } else {
+      s.info = h.cinfo.as<int32_t>() + (size_t)s.slot * 2 * Bz;
+      s.norms = h.cnorm.as<double>() + (size_t)s.slot * 4 * Bz;
+    }
+  }
+  {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
+    for (int q = 0; q < nseq; ++q) {
+      const ConicSeq& s = seq[q];
+      if (s.dir == CONIC_FWD)
+        hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, s.dA, s.db, s.dc, h.cx, vp, m, n,
+                           s.rhs);
+      else
+        hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, s.dx, h.cx, m, n, s.rhs);
+    }
+    check_launch();
+  }
+  if (h.sparse) conic_lsqr_sparse(h, seq, nseq);
+  else if (use_split(h)) conic_lsqr_split(h, seq, nseq);
+  else if (nseq == 1) conic_lsqr_one(h, seq[0]);
+  else if (seeds) conic_lsqr_seeds(h, seq, nseq);
+  else conic_lsqr_pair(h, seq[0], seq[1]);
+  if (seeds) copy_seed_info(h, h.cinfo.as<int32_t>(), h.cinfok.as<int32_t>());
+  bool any = false;
+  for (int q = 0; q < nseq; ++q) any |= seq_has_output(seq[q]);
+  // (a forward_reverse call brackets the output phase even with no output asked for, as it always has)
+  if (any || (nseq == 2 && !seeds)) {
+    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
+    for (int q = 0; q < nseq; ++q) {
+      const ConicSeq& s = seq[q];
+      if (!seq_has_output(s)) continue;
+      if (s.dir == CONIC_FWD)
+        hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, s.sol, h.cx, m, n, s.out_dx);
+      else
+        hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, s.sol, h.cx, vp, m, n, s.out_dA,
+                           s.out_db, s.out_dc);
+    }
+    check_launch();
+  }
+}
+
+void conic_forward(Handle& h, const double* dA, const double* db, const double* dc,
+                   double* out, double* out_dx) {
+  ConicSeq q = fwd_seq(dA, db, dc, out, out_dx, SLOT_LAST);
+  conic_run(h, &q, 1);
+}
+
+void conic_reverse(Handle& h, const double* dx, double* out_g, double* out_dA, double* out_db,
+                   double* out_dc) {
+  ConicSeq q = rev_seq(dx, out_g, out_dA, out_db, out_dc, SLOT_LAST);
+  conic_run(h, &q, 1);
+}
+
+void conic_forward_reverse(Handle& h, const double* dA, const double* db, const double* dc, const double* dx,
+                           double* out_f, double* out_dx, double* out_g, double* out_dA, double* out_db,
+                           double* out_dc) {
+  ConicSeq q[2] = {fwd_seq(dA, db, dc, out_f, out_dx, SLOT_FWD),
+                   rev_seq(dx, out_g, out_dA, out_db, out_dc, SLOT_LAST)};
+  conic_run(h, q, 2);
+}
+
+// seed j's block of a seed-major array of k·B·len doubles (null stays null)
+template <class T>
+static T* seed_block(T* p, int j, size_t len) { return p ? p + j * len : nullptr; }
 
 void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* out_dA, double* out_db,
                      double* out_dc) {
   if (k < 1) throw Error(-1, "dopt_conic_reverse_k: k must be at least 1");
-  if (!h.cfactored) conic_factor(h);
-  const int B = (int)h.batch, m = h.m, n = h.n;
-  const size_t N = (size_t)n + m + 1, Bz = (size_t)B;
-  h.cinfok.ensure((size_t)2 * std::max(B, 1) * k * sizeof(int32_t));
-  if (!multi_shared_sweep(h, k)) {
-    for (int j = k - 1; j >= 0; --j) {   // seed 0 last: the single-call info ends as its
-      conic_reverse(h, dx + j * Bz * n, out_g + j * Bz * N, out_dA ? out_dA + j * Bz * m * n : nullptr,
-                    out_db ? out_db + j * Bz * m : nullptr, out_dc ? out_dc + j * Bz * n : nullptr);
-      keep_seed_info(h, j);
-    }
-    return;
-  }
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)k * Bz * (wl + N) * sizeof(double));
-  double* rhs = h.cwork.as<double>() + (size_t)k * Bz * wl;
-  {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
-    for (int j = 0; j < k; ++j)
-      hipLaunchKernelGGL(conic_rev_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dx + j * Bz * n, h.cx, m, n,
-                         rhs + j * Bz * N);
-    check_launch();
-  }
-  conic_lsqr_k(h, k, 1e-4, rhs, out_g);   // per seed: `norm(dz) <= 1e-4` → g = 0 (ConicProgram.jl:369-370)
-  if (out_dA || out_db || out_dc) {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
-    for (int j = 0; j < k; ++j)
-      hipLaunchKernelGGL(conic_rev_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out_g + j * Bz * N, h.cx,
-                         h.vp.as<double>() + Bz * m, m, n, out_dA ? out_dA + j * Bz * m * n : nullptr,
-                         out_db ? out_db + j * Bz * m : nullptr, out_dc ? out_dc + j * Bz * n : nullptr);
-    check_launch();
-  }
+  const size_t B = h.batch, m = h.m, n = h.n, N = n + m + 1;
+  std::vector<ConicSeq> q(k);
+  for (int j = 0; j < k; ++j)
+    q[j] = rev_seq(seed_block(dx, j, B * n), seed_block(out_g, j, B * N), seed_block(out_dA, j, B * m * n),
+                   seed_block(out_db, j, B * m), seed_block(out_dc, j, B * n), SLOT_SEED0 + j);
+  conic_run(h, q.data(), k);
 }
 
 void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const double* dc, double* out,
                      double* out_dx) {
   if (k < 1) throw Error(-1, "dopt_conic_forward_k: k must be at least 1");
-  if (!h.cfactored) conic_factor(h);
-  const int B = (int)h.batch, m = h.m, n = h.n;
-  const size_t N = (size_t)n + m + 1, Bz = (size_t)B;
-  h.cinfok.ensure((size_t)2 * std::max(B, 1) * k * sizeof(int32_t));
-  if (!multi_shared_sweep(h, k)) {
-    for (int j = k - 1; j >= 0; --j) {
-      conic_forward(h, dA ? dA + j * Bz * m * n : nullptr, db ? db + j * Bz * m : nullptr,
-                    dc ? dc + j * Bz * n : nullptr, out + j * Bz * N, out_dx ? out_dx + j * Bz * n : nullptr);
-      keep_seed_info(h, j);
-    }
-    return;
-  }
-  const size_t wl = 5 * N + 3 * (size_t)m + n;
-  h.cwork.ensure((size_t)k * Bz * (wl + N) * sizeof(double));
-  double* rhs = h.cwork.as<double>() + (size_t)k * Bz * wl;
-  {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
-    for (int j = 0; j < k; ++j)
-      hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, dA ? dA + j * Bz * m * n : nullptr,
-                         db ? db + j * Bz * m : nullptr, dc ? dc + j * Bz * n : nullptr, h.cx,
-                         h.vp.as<double>() + Bz * m, m, n, rhs + j * Bz * N);
-    check_launch();
-  }
-  conic_lsqr_k(h, k, 0.0, rhs, out);   // per seed: RHS == 0 → 0 (ConicProgram.jl:320)
-  if (out_dx) {
-    PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
-    for (int j = 0; j < k; ++j)
-      hipLaunchKernelGGL(conic_fwd_out_kernel, dim3(B), dim3(CTPB), 0, h.stream, out + j * Bz * N, h.cx, m, n,
-                         out_dx + j * Bz * n);
-    check_launch();
-  }
+  const size_t B = h.batch, m = h.m, n = h.n, N = n + m + 1;
+  std::vector<ConicSeq> q(k);
+  for (int j = 0; j < k; ++j)
+    q[j] = fwd_seq(seed_block(dA, j, B * m * n), seed_block(db, j, B * m), seed_block(dc, j, B * n),
+                   seed_block(out, j, B * N), seed_block(out_dx, j, B * n), SLOT_SEED0 + j);
+  conic_run(h, q.data(), k);
 }
 
 }  // namespace dopt

@@ -458,6 +458,21 @@ void nlp_forward_reverse(Handle& h, const double* dp, const double* dxs, const d
                          double* ddual, double* dpo);
 void nlp_jacobian(Handle& h, double* ds);
 void nlp_kkt_solve(Handle& h, int k, const double* rhs, double* x, bool trans = false);
+// PSD triangle cones: a cone of dimension d(d+1)/2 is a d × d matrix.  psd_side
+// of a dimension that is not triangular is the largest side that fits.  The Dπ
+// apply and the eigensolver work on three images (psd_image_len) of dp × (dp + 1)
+// doubles each (psd_image), dp the side padded to a multiple of four.
+__host__ __device__ __forceinline__ int psd_tri_dim(int d) { return d * (d + 1) / 2; }
+__host__ __device__ __forceinline__ int psd_side(int dim) {
+  int d = 0;
+  while ((d + 1) * (d + 2) / 2 <= dim) ++d;
+  return d;
+}
+__host__ __device__ __forceinline__ size_t psd_image(int d) {
+  const int dp = (d + 3) & ~3;
+  return (size_t)dp * (dp + 1);
+}
+__host__ __device__ __forceinline__ size_t psd_image_len(int d) { return 3 * psd_image(d); }
 void conic_factor(Handle& h);
 void conic_forward(Handle& h, const double* dA, const double* db, const double* dc,
                    double* out, double* out_dx);

@@ -42,8 +42,18 @@ def _make(CB, d, B, n, cones, sparse=False):
 
 
 def _stats(e):
+    """(istop, iterations, norms) of the last single call."""
     st = e.lsqr_stats()
-    return st["istop"].copy(), st["iterations"].copy()
+    return st["istop"].copy(), st["iterations"].copy(), e.lsqr_norms()["last"].copy()
+
+
+def _check_seed0_slots(e, ref0, what):
+    """After a k-call the single-call getters report seed 0: stop code,
+    iteration count and the four norms, bitwise."""
+    st = e.lsqr_stats()
+    np.testing.assert_array_equal(st["istop"], ref0[0], err_msg=f"{what}: istop of seed 0")
+    np.testing.assert_array_equal(st["iterations"], ref0[1], err_msg=f"{what}: iterations of seed 0")
+    np.testing.assert_array_equal(e.lsqr_norms()["last"], ref0[2], err_msg=f"{what}: norms of seed 0")
 
 
 def _check_reverse_k(e, dx):
@@ -65,6 +75,7 @@ def _check_reverse_k(e, dx):
     # the single-call introspection reports seed 0
     np.testing.assert_array_equal(e.info(), ref[0][1][0])
     np.testing.assert_array_equal(e.iterations(), ref[0][1][1])
+    _check_seed0_slots(e, ref[0][1], "reverse_k")
     return got, st
 
 
@@ -82,6 +93,7 @@ def _check_forward_k(e, dA, db, dc):
         np.testing.assert_array_equal(st["istop"][j], ref[j][1][0], err_msg=f"forward seed {j}: istop")
         np.testing.assert_array_equal(st["iterations"][j], ref[j][1][1], err_msg=f"forward seed {j}: iterations")
     np.testing.assert_array_equal(e.iterations(), ref[0][1][1])
+    _check_seed0_slots(e, ref[0][1], "forward_k")
     return got, st
 
 
@@ -215,6 +227,87 @@ def test_fallback_routes_bitwise(SplitConicBatch, monkeypatch, route):
     dx, dA, db, dc = _normal_seeds(9, k, B, m, n)
     _check_reverse_k(e, dx)
     _check_forward_k(e, dA, db, dc)
+    e.close()
+
+
+def _slots(e):
+    """Everything the single-call getters hold: both [istop | iterations]
+    blocks and both norm blocks."""
+    st, nr = e.lsqr_stats(), e.lsqr_norms()
+    return {"last": (st["istop"].copy(), st["iterations"].copy(), nr["last"].copy()),
+            "fwd": (st["fwd_istop"].copy(), st["fwd_iterations"].copy(), nr["fwd"].copy())}
+
+
+def _assert_slot(got, ref, what):
+    for a, b, name in zip(got, ref, ("istop", "iterations", "norms")):
+        np.testing.assert_array_equal(a, b, err_msg=f"{what}: {name}")
+
+
+@pytest.mark.parametrize("route", ["persistent", "split-fused", "split-six-launch", "sparse"])
+def test_info_slots_across_calls(ConicBatch, monkeypatch, route):
+    """forward_reverse leaves the reverse run's statistics and norms in the
+    "last" slots and the forward run's in the "fwd" slots, each bitwise what
+    the separate call reports; a later single call rewrites "last" only."""
+    from diffopt_amd.synthetic import conic_numpy
+    if route.startswith("split"):
+        monkeypatch.setenv("DOPT_CONIC_SPLIT", "1")
+        if route == "split-six-launch":
+            monkeypatch.setenv("DOPT_SPLIT_FUSE", "0")
+    else:
+        monkeypatch.delenv("DOPT_CONIC_SPLIT", raising=False)
+    B, n = 3, 30
+    d = conic_numpy(B, n, MIXED, 11)
+    e = _make(ConicBatch, d, B, n, MIXED, sparse=route == "sparse")
+    e.forward_reverse(d["dx"], d["dA"], d["db"], d["dc"])
+    both = _slots(e)
+    e.forward(d["dA"], d["db"], d["dc"])
+    fwd = _slots(e)
+    _assert_slot(both["fwd"], fwd["last"], "forward_reverse's fwd slots against forward")
+    _assert_slot(fwd["fwd"], both["fwd"], "fwd slots after a single forward")
+    e.reverse(d["dx"])
+    rev = _slots(e)
+    _assert_slot(both["last"], rev["last"], "forward_reverse's last slots against reverse")
+    _assert_slot(rev["fwd"], both["fwd"], "fwd slots after a single reverse")
+    assert np.all(both["fwd"][1] > 0) and np.all(both["last"][1] > 0)   # both runs iterated
+    e.close()
+
+
+# phase counts per call as dopt_get_phase_times reports them, from a run of
+# commit c059bfe (the parent of the call-table refactor): on the persistent
+# route every call brackets each phase once; on the split route a _k call
+# runs seed by seed, so each phase is bracketed once per seed
+_ONCE = {"conic_rhs": 1, "conic_lsqr": 1, "conic_output": 1}
+_PER_SEED = {"conic_rhs": 3, "conic_lsqr": 3, "conic_output": 3}
+PHASE_COUNTS = {"persistent": {"reverse_k": _ONCE, "forward_k": _ONCE, "forward_reverse": _ONCE, "reverse": _ONCE,
+                               "forward": _ONCE},
+                "split": {"reverse_k": _PER_SEED, "forward_k": _PER_SEED, "forward_reverse": _ONCE, "reverse": _ONCE,
+                          "forward": _ONCE}}
+
+
+@pytest.mark.parametrize("route", ["persistent", "split"])
+def test_phase_counts_per_call(ConicBatch, monkeypatch, route):
+    from diffopt_amd.synthetic import conic_numpy
+    if route == "split":
+        monkeypatch.setenv("DOPT_CONIC_SPLIT", "1")
+    else:
+        monkeypatch.delenv("DOPT_CONIC_SPLIT", raising=False)
+    B, n, k = 2, 30, 3
+    m = sum(dim for _, dim in MIXED)
+    d = conic_numpy(B, n, MIXED, 11)
+    e = _make(ConicBatch, d, B, n, MIXED)
+    e.factor()
+    e.set_profiling(True)
+    dx, dA, db, dc = _normal_seeds(3, k, B, m, n)
+    calls = {"reverse_k": lambda: e.reverse_k(dx),
+             "forward_k": lambda: e.forward_k(dA, db, dc),
+             "forward_reverse": lambda: e.forward_reverse(dx[0], dA[0], db[0], dc[0]),
+             "reverse": lambda: e.reverse(dx[0]),
+             "forward": lambda: e.forward(dA[0], db[0], dc[0])}
+    for name, call in calls.items():
+        call()
+        got = {ph: cnt for ph, (_, cnt) in e.phase_times().items()}
+        print(f"[phases] {route} {name}: {got}")
+        assert got == PHASE_COUNTS[route][name], (route, name, got)
     e.close()
 
 
