@@ -216,6 +216,10 @@ int dopt_destroy(dopt_handle* h) {
   for (auto& b : h->csc_in) b.release();
   for (auto& b : h->csc_in_val) b.release();
   h->csc_err.release();
+  for (auto& st : h->spt)
+    for (DevBuf* b : {&st.cp, &st.ri, &st.rp, &st.ci, &st.rv}) b->release();
+  for (auto& b : h->spt_in) b.release();
+  for (auto& b : h->spt_val) b.release();
   for (auto& b : h->own_cin) b.release();
   for (auto& b : h->tin) b.release();
   for (auto& b : h->tout) b.release();
@@ -902,6 +906,151 @@ int dopt_qp_forward_reverse(dopt_handle* h, const double* dl_dz, const double* d
   });
 }
 
+// ---- `_csc` calls: sparse tangents, gradients on a pattern --------------------
+// One tangent / pattern of a `_csc` call on the device: the host-side argument
+// checks, then host mode copies into the handle's per-call buffers (slot k of
+// spt_in / spt_val), device mode borrows.  nzval == false: a pattern.
+static dopt::CscArg stage_csc(Handle& h, int k, const int64_t* cp, const int64_t* rv, const double* nz, int64_t nnz,
+                              bool nzval) {
+  dopt::CscArg a{nullptr, nullptr, nullptr, 0};
+  if (!cp) return a;
+  if (nnz < 0) throw Error(-1, "nnz must be >= 0");
+  if (nnz > 0 && (!rv || (nzval && !nz))) throw Error(-1, "rowval and nzval are required when nnz > 0");
+  a.cp = stage_in_i64(h, h.spt_in[2 * k], cp, (size_t)h.batch * (h.n + 1));
+  a.rv = nnz ? stage_in_i64(h, h.spt_in[2 * k + 1], rv, (size_t)nnz) : nullptr;
+  a.nz = nzval && nnz ? stage_in(h, h.spt_val[k], nz, (size_t)nnz) : nullptr;
+  a.nnz = nnz;
+  return a;
+}
+
+// the device error word of a `_csc` call's staging, cleared
+static int* csc_err_clear(Handle& h) {
+  h.csc_err.ensure(sizeof(int));
+  DOPT_CHECK_HIP(hipMemsetAsync(h.csc_err.p, 0, sizeof(int), h.stream));
+  return h.csc_err.as<int>();
+}
+// ... its read-back queued behind the call's work (it lands with the call's
+// final wait), and raised after that wait
+static void csc_err_queue(Handle& h, int* herr) {
+  DOPT_CHECK_HIP(hipMemcpyAsync(herr, h.csc_err.p, sizeof(int), hipMemcpyDeviceToHost, h.stream));
+}
+static void csc_err_raise(int herr) {
+  if (const char* msg = dopt::sp_err_message(herr)) throw Error(-1, msg);
+}
+static void csc_err_wait(Handle& h) {
+  int herr = 0;
+  csc_err_queue(h, &herr);
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+  csc_err_raise(herr);
+}
+
+static void qp_csc_route_check(Handle& h, const char* name, const char* dense_name) {
+  if (h.kind != DOPT_KIND_QP) throw Error(-1, std::string(name) + " on a non-QP handle");
+  if (!h.sparse)
+    throw Error(-1, std::string(name) + ": sparse-route handles only (dopt_set_sparse); a dense-route handle takes " +
+                        dense_name);
+  if (!h.set) throw Error(-1, std::string(name) + ": dopt_qp_set_csc has not been called");
+}
+
+int dopt_qp_forward_csc(dopt_handle* h,
+                        const int64_t* dQ_colptr, const int64_t* dQ_rowval, const double* dQ_nzval, int64_t dQ_nnz,
+                        const double* dq,
+                        const int64_t* dG_colptr, const int64_t* dG_rowval, const double* dG_nzval, int64_t dG_nnz,
+                        const double* dh,
+                        const int64_t* dA_colptr, const int64_t* dA_rowval, const double* dA_nzval, int64_t dA_nnz,
+                        const double* db, double* out) {
+  return guarded(h, [&]() {
+    qp_csc_route_check(*h, "dopt_qp_forward_csc", "dopt_qp_forward");
+    if (!out) throw Error(-1, "out is required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
+    const dopt::CscArg T[3] = {stage_csc(*h, 0, dQ_colptr, dQ_rowval, dQ_nzval, dQ_nnz, true),
+                               stage_csc(*h, 1, m ? dG_colptr : nullptr, dG_rowval, dG_nzval, dG_nnz, true),
+                               stage_csc(*h, 2, p ? dA_colptr : nullptr, dA_rowval, dA_nzval, dA_nnz, true)};
+    const double* b = stage_in(*h, h->tin[2], dq, B * n);
+    const double* d = stage_in(*h, h->tin[4], m ? dh : nullptr, B * m);
+    const double* f = stage_in(*h, h->tin[6], p ? db : nullptr, B * p);
+    double* o = out_ptr(*h, h->tout[1], out, B * L);
+    int* err = csc_err_clear(*h);
+    dopt::sp_forward_csc(*h, T, b, d, f, o, err);
+    copy_out(*h, out, o, B * L);
+    csc_err_wait(*h);
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_qp_forward_reverse_csc(dopt_handle* h, const double* dl_dz,
+                                const int64_t* dQ_colptr, const int64_t* dQ_rowval, const double* dQ_nzval,
+                                int64_t dQ_nnz, const double* dq,
+                                const int64_t* dG_colptr, const int64_t* dG_rowval, const double* dG_nzval,
+                                int64_t dG_nnz, const double* dh,
+                                const int64_t* dA_colptr, const int64_t* dA_rowval, const double* dA_nzval,
+                                int64_t dA_nnz, const double* db, double* out_rev, double* out_fwd) {
+  return guarded(h, [&]() {
+    qp_csc_route_check(*h, "dopt_qp_forward_reverse_csc", "dopt_qp_forward_reverse");
+    if (!dl_dz || !out_rev || !out_fwd) throw Error(-1, "dl_dz, out_rev and out_fwd are required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
+    const dopt::CscArg T[3] = {stage_csc(*h, 0, dQ_colptr, dQ_rowval, dQ_nzval, dQ_nnz, true),
+                               stage_csc(*h, 1, m ? dG_colptr : nullptr, dG_rowval, dG_nzval, dG_nnz, true),
+                               stage_csc(*h, 2, p ? dA_colptr : nullptr, dA_rowval, dA_nzval, dA_nnz, true)};
+    const double* r = stage_in(*h, h->tin[0], dl_dz, B * n);
+    const double* b = stage_in(*h, h->tin[2], dq, B * n);
+    const double* d = stage_in(*h, h->tin[4], m ? dh : nullptr, B * m);
+    const double* f = stage_in(*h, h->tin[6], p ? db : nullptr, B * p);
+    double* o1 = out_ptr(*h, h->tout[0], out_rev, B * L);
+    double* o2 = out_ptr(*h, h->tout[1], out_fwd, B * L);
+    int* err = csc_err_clear(*h);
+    h->factored = false;   // as dopt_qp_forward_reverse: one solve = factor + fwd + rev
+    dopt::sp_forward_reverse_csc(*h, r, T, b, d, f, o1, o2, err);
+    copy_out(*h, out_rev, o1, B * L);
+    copy_out(*h, out_fwd, o2, B * L);
+    csc_err_wait(*h);
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+// An on-pattern gradient's values through the staging buffers: host mode
+// copies the caller's array in first, so that the entries no problem's range
+// covers come back as they were
+static double* nz_out_ptr(Handle& h, DevBuf& buf, double* dst, size_t count) {
+  if (!dst || h.mem == DOPT_MEM_DEVICE) return dst;
+  buf.ensure(std::max<size_t>(count, 1) * sizeof(double));
+  if (count) DOPT_CHECK_HIP(hipMemcpyAsync(buf.p, dst, count * sizeof(double), hipMemcpyHostToDevice, h.stream));
+  return buf.as<double>();
+}
+
+int dopt_qp_reverse_grads_csc(dopt_handle* h, const double* rev,
+                              const int64_t* Q_colptr, const int64_t* Q_rowval, int64_t Q_nnz, double* out_dQ_nz,
+                              const int64_t* G_colptr, const int64_t* G_rowval, int64_t G_nnz, double* out_dG_nz,
+                              const int64_t* A_colptr, const int64_t* A_rowval, int64_t A_nnz, double* out_dA_nz) {
+  return guarded(h, [&]() {
+    qp_csc_route_check(*h, "dopt_qp_reverse_grads_csc", "dopt_qp_reverse_grads");
+    if (!rev) throw Error(-1, "rev is required");
+    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
+    if (out_dQ_nz && !Q_colptr)
+      throw Error(-1, "dopt_qp_reverse_grads_csc: the sparse route keeps no Q pattern; pass one");
+    double* outs[3] = {out_dQ_nz, m ? out_dG_nz : nullptr, p ? out_dA_nz : nullptr};
+    const dopt::CscArg P[3] = {stage_csc(*h, 0, outs[0] ? Q_colptr : nullptr, Q_rowval, nullptr, Q_nnz, false),
+                               stage_csc(*h, 1, outs[1] ? G_colptr : nullptr, G_rowval, nullptr, G_nnz, false),
+                               stage_csc(*h, 2, outs[2] ? A_colptr : nullptr, A_rowval, nullptr, A_nnz, false)};
+    const double* r = stage_in(*h, h->tin[0], rev, B * L);
+    size_t cnt[3];
+    double* dev[3];
+    for (int k = 0; k < 3; ++k) {
+      cnt[k] = !outs[k] ? 0 : P[k].cp ? (size_t)P[k].nnz : (size_t)h->sp[k - 1].nnz;
+      dev[k] = nz_out_ptr(*h, h->tout[k], outs[k], cnt[k]);
+    }
+    int* err = csc_err_clear(*h);
+    dopt::sp_reverse_grads_at(*h, r, P, dev, err);
+    for (int k = 0; k < 3; ++k) copy_out(*h, outs[k], dev[k], cnt[k]);
+    csc_err_wait(*h);
+    return 0;
+  });
+}
+
 // ---- NonLinearProgram back-end ---------------------------------------------
 
 int dopt_nlp_set_structure(dopt_handle* h, const int32_t* con_kind, const int8_t* has_low,
@@ -1480,7 +1629,7 @@ int dopt_conic_set_csc(dopt_handle* h, const int64_t* A_colptr, const int64_t* A
       for (int k = 0; k < ncones && cone_desc; ++k)
         if (cone_desc[2 * k] == DOPT_CONE_PSD_TRI && cone_desc[2 * k + 1] > dopt::psd_tri_dim(64))
           throw Error(-1, "sparse conic route: PSD cones up to side 64 (their Dπ apply runs in LDS)");
-      if (m) dopt::sp_stage(*h, 0, cp, rv ? rv : cp, nz, A_nnz, (int)m, h->csc_err.as<int>());
+      if (m) dopt::sp_stage(*h, h->sp[0], cp, rv ? rv : cp, nz, A_nnz, (int)m, h->csc_err.as<int>());
     } else {
       DevBuf& d = h->own_cin[0];
       d.ensure(std::max<size_t>(B * m * n, 1) * sizeof(double));
@@ -1623,6 +1772,88 @@ int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const doub
                [&](const double** i, double** o) { dopt::conic_forward_k(*h, k, i[0], i[1], i[2], o[0], o[1]); });
     h->conic_k = k;
     h->last_time = tm.s();
+    return 0;
+  });
+}
+
+// The tangent dA of a conic `_csc` call into h.spt[0] (the staging counts as
+// right-hand-side time); false: absent, the call takes the dense entry's path
+// with dA == null
+static bool conic_stage_tangent(Handle& h, const int64_t* cp, const int64_t* rv, const double* nz, int64_t nnz) {
+  if (!h.cset) throw Error(-1, "no conic model is set (dopt_conic_set / dopt_conic_set_csc)");
+  const dopt::CscArg T = stage_csc(h, 0, h.m ? cp : nullptr, rv, nz, nnz, true);
+  if (!T.cp) return false;
+  int* err = csc_err_clear(h);
+  dopt::PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
+  dopt::sp_stage(h, h.spt[0], T.cp, T.rv ? T.rv : T.cp, T.nz, T.nnz, h.m, err, true);
+  return true;
+}
+
+int dopt_conic_forward_csc(dopt_handle* h, const int64_t* dA_colptr, const int64_t* dA_rowval,
+                           const double* dA_nzval, int64_t dA_nnz, const double* db, const double* dc,
+                           double* out, double* out_dx) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_forward_csc on a non-conic handle");
+    h->conic_k = 0;
+    if (!out) throw Error(-1, "out is required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
+    const bool sp = conic_stage_tangent(*h, dA_colptr, dA_rowval, dA_nzval, dA_nnz);
+    int herr = 0;
+    conic_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+               [&](const double** i, double** o) {
+                 if (sp) dopt::conic_forward_csc(*h, h->spt[0], h->csc_err.as<int>(), i[0], i[1], o[0], o[1]);
+                 else dopt::conic_forward(*h, nullptr, i[0], i[1], o[0], o[1]);
+                 if (sp) csc_err_queue(*h, &herr);
+               });
+    csc_err_raise(herr);
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_conic_forward_reverse_csc(dopt_handle* h, const int64_t* dA_colptr, const int64_t* dA_rowval,
+                                   const double* dA_nzval, int64_t dA_nnz, const double* db, const double* dc,
+                                   const double* dx, double* out, double* out_dx, double* out_g,
+                                   double* out_db, double* out_dc) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_forward_reverse_csc on a non-conic handle");
+    h->conic_k = 0;
+    if (!out || !dx || !out_g) throw Error(-1, "out, dx and out_g are required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
+    const bool sp = conic_stage_tangent(*h, dA_colptr, dA_rowval, dA_nzval, dA_nnz);
+    int herr = 0;
+    conic_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
+               {{out, 0, B * N}, {out_dx, 1, B * n}, {out_g, 2, B * N}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
+               [&](const double** i, double** o) {
+                 if (sp)
+                   dopt::conic_forward_reverse_csc(*h, h->spt[0], h->csc_err.as<int>(), i[0], i[1], i[2], o[0], o[1],
+                                                   o[2], o[3], o[4]);
+                 else
+                   dopt::conic_forward_reverse(*h, nullptr, i[0], i[1], i[2], o[0], o[1], o[2], nullptr, o[3], o[4]);
+                 if (sp) csc_err_queue(*h, &herr);
+               });
+    csc_err_raise(herr);
+    h->last_time = tm.s();
+    return 0;
+  });
+}
+
+int dopt_conic_reverse_grads_csc(dopt_handle* h, const double* g, const int64_t* P_colptr,
+                                 const int64_t* P_rowval, int64_t P_nnz, double* out_nz) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_reverse_grads_csc on a non-conic handle");
+    if (!g || !out_nz) throw Error(-1, "g and out_nz are required");
+    const size_t B = h->batch, N = (size_t)h->n + h->m + 1;
+    const dopt::CscArg P = stage_csc(*h, 0, P_colptr, P_rowval, nullptr, P_nnz, false);
+    const size_t cnt = P.cp ? (size_t)P.nnz : h->sparse ? (size_t)h->sp[0].nnz : 0;   // (refusals: conic_reverse_grads_at)
+    const double* gd = stage_in(*h, h->tin[0], g, B * N);
+    double* o = nz_out_ptr(*h, h->tout[3], out_nz, cnt);
+    int* err = csc_err_clear(*h);
+    dopt::conic_reverse_grads_at(*h, gd, P, o, err);
+    copy_out(*h, out_nz, o, cnt);
+    csc_err_wait(*h);
     return 0;
   });
 }

@@ -1394,6 +1394,91 @@ __global__ __launch_bounds__(CTPB) void conic_rev_out_kernel(
   }
 }
 
+// forward RHS from a sparse tangent with its own pattern (the reference's
+// `dA = sparse(dAi, dAj, dAv, lines, cols)`, which enters only through
+// `dA' * vp` and `dA * u`: ConicProgram.jl:288-305, :314-318), staged as CSC plus
+// CSR like the sparse route's A_moi.  One workgroup per problem, and
+// conic_fwd_rhs_kernel's sums in its own order: (dAᵀvp)_j by a wave per CSC
+// column whose lanes hold that kernel's per-lane partial sums
+// (sparse_col_lane_sum), (dA x)_i by one thread walking the CSR row (columns
+// ascending), then the same epilogue and last entry.  So the right-hand side —
+// and with it the LSQR run — is bit-identical to the dense-tangent call's on
+// the densified tangent (finite x, vp; a tangent without duplicate entries,
+// rows sorted within a column), and an absent or empty tangent gives
+// dA == null's bits.  Per-output lane groups (SparseA<G>::pair) sum in another
+// order; two LSQR runs from right-hand sides that differ in the last bits can
+// stop an iteration or two apart and then agree only to ≈ 1e-7.  A staging
+// error (*err != 0, raised by the host after the call's wait) leaves the
+// tangent unread.
+__global__ __launch_bounds__(CTPB) void conic_fwd_rhs_csc_kernel(
+    SpConic dA, const int* __restrict__ err, const double* __restrict__ db, const double* __restrict__ dc,
+    const double* __restrict__ x, const double* __restrict__ vp, int m, int n, double* __restrict__ rhs) {
+  __shared__ double red[4];
+  const int b = blockIdx.x, t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int N = n + m + 1;
+  const bool ok = *err == 0;
+  const double* xb = x + (size_t)b * n;
+  const double* vpb = vp + (size_t)b * m;
+  double* r = rhs + (size_t)b * N;
+  const int64_t* cp = dA.cp + (size_t)b * (n + 1);
+  const int64_t* rp = dA.rp + (size_t)b * (m + 1);
+  for (int j = wv; j < n; j += CTPB / 64) {
+    double acc = 0.0;
+    if (ok) acc = sparse_col_lane_sum(dA.ri, dA.cv, cp[j], cp[j + 1], vpb, acc);
+    acc = cwave_sum(acc);
+    if (lane == 0) r[j] = acc + (dc ? dc[(size_t)b * n + j] : 0.0);
+  }
+  for (int i = t; i < m; i += CTPB) {
+    double acc = 0.0;
+    if (ok)
+      for (int64_t k = rp[i]; k < rp[i + 1]; ++k) acc = fma(dA.rv[k], xb[dA.ci[k]], acc);
+    r[n + i] = -acc + (db ? db[(size_t)b * m + i] : 0.0);
+  }
+  double cu = 0.0, bv = 0.0;
+  if (dc) for (int j = t; j < n; j += CTPB) cu = fma(dc[(size_t)b * n + j], xb[j], cu);
+  if (db) for (int i = t; i < m; i += CTPB) bv = fma(db[(size_t)b * m + i], vpb[i], bv);
+  const double s = cblock_sum(cu, red);
+  const double s2 = cblock_sum(bv, red);
+  if (t == 0) r[n + m] = -s - s2;
+}
+
+// dA at the entries of a pattern: out_nz[k] = g_v[i]·x[j] − vp[i]·g_x[j] for
+// entry k = (i, j) of problem b (the reference's lazy `_get_dA` read at the
+// requested entries, ConicProgram.jl:430-443).  Grid (column chunk, problem):
+// the column from the loop, the row from rowval, one entry per thread, lanes
+// over consecutive k; an entry index no problem's range covers is left
+// untouched.  `base` = 1 for a caller's Julia arrays (validated here: error
+// bit 1 colptr, 2 rowval), 0 for the sparse handle's own staged A_moi.  The
+// entry expression restates conic_rev_out_kernel's — change both together.
+template <class RT>
+__global__ __launch_bounds__(CTPB) void conic_dA_at_kernel(
+    const double* __restrict__ g, const double* __restrict__ x, const double* __restrict__ vp, int m, int n, int B,
+    const int64_t* __restrict__ colptr, const RT* __restrict__ rowval, int base, int64_t nnz,
+    double* __restrict__ out, int* __restrict__ err) {
+  const int N = n + m + 1;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t* cp = colptr + (size_t)b * (n + 1);
+    const double* gb = g + (size_t)b * N;
+    const double* xb = x + (size_t)b * n;
+    const double* vpb = vp + (size_t)b * m;
+    for (int j = blockIdx.x; j < n; j += gridDim.x) {
+      const int64_t k0 = cp[j] - base, k1 = cp[j + 1] - base;
+      if (k0 < 0 || k1 < k0 || k1 > nnz) {
+        if (threadIdx.x == 0) atomicOr(err, 1);
+        continue;
+      }
+      for (int64_t k = k0 + threadIdx.x; k < k1; k += CTPB) {
+        const int64_t i = (int64_t)rowval[k] - base;
+        if (i < 0 || i >= m) {
+          atomicOr(err, 2);
+          continue;
+        }
+        out[k] = gb[n + i] * xb[j] - vpb[i] * gb[j];
+      }
+    }
+  }
+}
+
 // ---------------------------------------------------------------------------
 // Split LSQR: the same iteration as conic_lsqr_kernel, but each M / Mᵀ apply
 // is spread over a (row block × problem) grid so that a few large problems
@@ -2345,6 +2430,8 @@ enum { SLOT_LAST = 0, SLOT_FWD = 1, SLOT_SEED0 = 2 };
 struct ConicSeq {
   ConicDir dir;
   const double *dA, *db, *dc;   // forward: the tangents (each may be null)
+  const SpStore* dA_sp;         // forward: dA as a staged sparse tangent instead (null: the dense dA above)
+  const int* dA_err;            // ... and its staging's device error word
   const double* dx;             // reverse: the seed
   double* sol;                  // LSQR's solution, N per problem: forward's out, reverse's g
   double* out_dx;               // forward: ForwardVariablePrimal (null: not wanted)
@@ -2738,7 +2825,13 @@ static void conic_run(Handle& h, ConicSeq* seq, int nseq) {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
     for (int q = 0; q < nseq; ++q) {
       const ConicSeq& s = seq[q];
-      if (s.dir == CONIC_FWD)
+      if (s.dir == CONIC_FWD && s.dA_sp) {
+        const SpStore& st = *s.dA_sp;
+        const SpConic T{st.cp.as<int64_t>(), st.rp.as<int64_t>(), st.ri.as<int32_t>(), st.ci.as<int32_t>(), st.cv,
+                        st.rv.as<double>()};
+        hipLaunchKernelGGL(conic_fwd_rhs_csc_kernel, dim3(B), dim3(CTPB), 0, h.stream, T, s.dA_err, s.db, s.dc, h.cx, vp,
+                           m, n, s.rhs);
+      } else if (s.dir == CONIC_FWD)
         hipLaunchKernelGGL(conic_fwd_rhs_kernel, dim3(B), dim3(CTPB), 0, h.stream, s.dA, s.db, s.dc, h.cx, vp, m, n,
                            s.rhs);
       else
@@ -2788,6 +2881,44 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
   ConicSeq q[2] = {fwd_seq(dA, db, dc, out_f, out_dx, SLOT_FWD),
                    rev_seq(dx, out_g, out_dA, out_db, out_dc, SLOT_LAST)};
   conic_run(h, q, 2);
+}
+
+void conic_forward_csc(Handle& h, const SpStore& dA, const int* err, const double* db, const double* dc, double* out,
+                       double* out_dx) {
+  ConicSeq q = fwd_seq(nullptr, db, dc, out, out_dx, SLOT_LAST);
+  q.dA_sp = &dA, q.dA_err = err;
+  conic_run(h, &q, 1);
+}
+
+void conic_forward_reverse_csc(Handle& h, const SpStore& dA, const int* err, const double* db, const double* dc,
+                               const double* dx, double* out_f, double* out_dx, double* out_g, double* out_db,
+                               double* out_dc) {
+  ConicSeq q[2] = {fwd_seq(nullptr, db, dc, out_f, out_dx, SLOT_FWD),
+                   rev_seq(dx, out_g, nullptr, out_db, out_dc, SLOT_LAST)};
+  q[0].dA_sp = &dA, q[0].dA_err = err;
+  conic_run(h, q, 2);
+}
+
+void conic_reverse_grads_at(Handle& h, const double* g, const CscArg& P, double* out_nz, int* err) {
+  if (!h.cset || !h.cfactored)
+    throw Error(-1, "dopt_conic_reverse_grads_csc: needs a factored handle (x and vp of dopt_conic_factor)");
+  const int B = (int)h.batch, m = h.m, n = h.n;
+  if (m == 0 || n == 0) return;
+  const double* vp = h.vp.as<double>() + (size_t)B * m;
+  const dim3 grid(std::max(1, std::min(n, 1024)), std::min(B, 65535));
+  PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
+  if (P.cp) {
+    hipLaunchKernelGGL(conic_dA_at_kernel<int64_t>, grid, dim3(CTPB), 0, h.stream, g, h.cx, vp, m, n, B, P.cp,
+                       P.rv ? P.rv : P.cp, 1, P.nnz, out_nz, err);
+  } else {
+    if (!h.sparse)
+      throw Error(-1, "dopt_conic_reverse_grads_csc: only a sparse-route handle keeps the pattern of "
+                      "dopt_conic_set_csc; pass the pattern");
+    const SpStore& st = h.sp[0];
+    hipLaunchKernelGGL(conic_dA_at_kernel<int32_t>, grid, dim3(CTPB), 0, h.stream, g, h.cx, vp, m, n, B,
+                       st.cp.as<int64_t>(), st.ri.as<int32_t>(), 0, st.nnz, out_nz, err);
+  }
+  check_launch();
 }
 
 // seed j's block of a seed-major array of k·B·len doubles (null stays null)

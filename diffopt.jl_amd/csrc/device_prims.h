@@ -70,6 +70,34 @@ __device__ __forceinline__ double wave_sum63(double v) {
 // the DPP sum in every lane: broadcast from lane 63
 __device__ __forceinline__ double cwave_sum(double v) { return readlane_d(wave_sum63(v), 63); }
 
+// The per-lane partial sums of a dense column sweep by one wave,
+//   for (i = lane; i < rows; i += 64) acc = fma(col[i], w[i], acc),
+// from the column's sparse entries k0 ≤ k < k1 (rows ri ascending, values cv):
+// lane L adds the entries with ri % 64 == L in ascending order, so each lane
+// ends with the dense sweep's bits (an absent entry is a zero there, and
+// fma(0, w, acc) == acc for finite w).  The wave walks the entries 64 at a
+// time (coalesced loads) and hands each to its lane by broadcast.  Called by
+// all 64 lanes with wave-uniform k0, k1.
+__device__ __forceinline__ double sparse_col_lane_sum(const int32_t* __restrict__ ri, const double* __restrict__ cv,
+                                                      int64_t k0, int64_t k1, const double* __restrict__ w,
+                                                      double acc) {
+  const int lane = threadIdx.x & 63;
+  for (int64_t c = k0; c < k1; c += 64) {
+    const int64_t k = c + lane;
+    const bool in = k < k1;
+    const int i = in ? ri[k] : 0;
+    const double a = in ? cv[k] : 0.0;
+    const double wi = in ? w[i] : 0.0;
+    const int cnt = k1 - c < 64 ? (int)(k1 - c) : 64;
+    for (int t = 0; t < cnt; ++t) {
+      const int it = __shfl(i, t);
+      const double at = __shfl(a, t), wt = __shfl(wi, t);
+      if ((it & 63) == lane) acc = fma(at, wt, acc);
+    }
+  }
+  return acc;
+}
+
 // ---- block sums -------------------------------------------------------------
 // Every thread gets the result; `red` = LDS scratch of one double per wave.
 // They differ in summation order, so each kernel keeps the one it was

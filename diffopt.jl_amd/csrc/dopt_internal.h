@@ -143,6 +143,13 @@ struct QPIn {
 struct FwdTangents {
   const double *dQ, *dq, *dG, *dh, *dA, *db;
 };
+// One batched CSC matrix of the `_csc` entries as the ABI takes it (device
+// pointers, Julia's 1-based arrays; cp == nullptr: absent; nz unused for a pattern)
+struct CscArg {
+  const int64_t *cp, *rv;
+  const double* nz;
+  int64_t nnz;
+};
 
 struct Handle {
   int device = 0;
@@ -223,6 +230,10 @@ struct Handle {
   bool sparse = false;
   bool sp_qnz = false;             // some problem's Q has a non-zero value (needs an LU this route lacks)
   SpStore sp[2];                   // G, A
+  // the `_csc` calls' tangents (dQ, dG, dA; the conic dA: slot 0), staged like the model's matrices but per
+  // call: nothing in them is read by a later call, and the model's stores above are never touched
+  SpStore spt[3];
+  DevBuf spt_in[6], spt_val[3];    // host-mode copies of the tangents' / patterns' colptr and rowval, and nzval
   DevBuf sp_tmp, sp_sort, sp_s, sp_ws, sp_info, sp_rhs;
 
   // ---- CONIC ----
@@ -440,9 +451,21 @@ void sp_set_csc(Handle& h, const int64_t* Qcp, const int64_t* Qrv, const double*
                 const int64_t* Gcp, const int64_t* Grv, const double* Gnz, int64_t Gnnz, const int64_t* Acp,
                 const int64_t* Arv, const double* Anz, int64_t Annz, int* err);
 void sp_factor(Handle& h);
-// one CSC matrix (rows × n) into h.sp[slot]: converted, validated, CSR copy built (the conic route's A_moi: slot 0)
-void sp_stage(Handle& h, int slot, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t nnz,
-              int rows, int* err);
+// one CSC matrix (rows × n) into `st`: converted, validated, CSR copy built (the conic route's A_moi: h.sp[0]).
+// disjoint: also require the problems' colptr ranges ascending and disjoint (error bit 8; the `_csc` tangents)
+void sp_stage(Handle& h, SpStore& st, const int64_t* colptr, const int64_t* rowval, const double* nzval, int64_t nnz,
+              int rows, int* err, bool disjoint = false);
+// the message of a staging error word (bits 1, 2, 8), null for none
+const char* sp_err_message(int err);
+// the `_csc` calls of the sparse QP route: T[3] = dQ, dG, dA (absent, or staged here into h.spt); `err` is the
+// device error word of the staging, which the right-hand side kernel reads (a refused tangent is never dereferenced)
+void sp_forward_csc(Handle& h, const CscArg* T, const double* dq, const double* dh, const double* db, double* out,
+                    int* err);
+void sp_forward_reverse_csc(Handle& h, const double* dl_dz, const CscArg* T, const double* dq, const double* dh,
+                            const double* db, double* out_rev, double* out_fwd, int* err);
+// reverse gradients sampled on patterns: P[3] = Q, G, A patterns (cp == nullptr with out[k] != nullptr: the handle's
+// own G / A), out[k] = the values per entry (nullptr: skipped)
+void sp_reverse_grads_at(Handle& h, const double* rev, const CscArg* P, double* const* out, int* err);
 void sp_reverse(Handle& h, const double* dl_dz, double* out);
 void sp_forward(Handle& h, const FwdTangents& T, double* out);
 void sp_forward_reverse(Handle& h, const double* dl_dz, const FwdTangents& T, double* out_rev, double* out_fwd);
@@ -483,6 +506,14 @@ void conic_forward_reverse(Handle& h, const double* dA, const double* db, const 
                            double* out_dc);
 void conic_reverse_k(Handle& h, int k, const double* dx, double* out_g, double* out_dA, double* out_db,
                      double* out_dc);
+// dopt_conic_forward_csc / _forward_reverse_csc: the tangent dA staged in `dA` (sp_stage), `err` its device error word
+void conic_forward_csc(Handle& h, const SpStore& dA, const int* err, const double* db, const double* dc, double* out,
+                       double* out_dx);
+void conic_forward_reverse_csc(Handle& h, const SpStore& dA, const int* err, const double* db, const double* dc,
+                               const double* dx, double* out_f, double* out_dx, double* out_g, double* out_db,
+                               double* out_dc);
+// out_nz[k] = g[n+i]·x[j] − vp[i]·g[j] at the entries of a pattern (P.cp == nullptr: the sparse handle's own A_moi)
+void conic_reverse_grads_at(Handle& h, const double* g, const CscArg& P, double* out_nz, int* err);
 void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const double* dc, double* out,
                      double* out_dx);
 

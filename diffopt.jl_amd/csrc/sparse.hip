@@ -138,6 +138,14 @@ __global__ void sp_qtest_kernel(const double* __restrict__ nz, int64_t nnz, int*
   if (__any(bad) && (threadIdx.x & 63) == 0) atomicOr(err, 4);
 }
 
+// The `_csc` tangents: the problems' entry ranges must be ascending and
+// disjoint, cp_b[0] ≥ cp_{b−1}[ncols] (the CSR build writes one key per entry
+// index); bit 8 of err otherwise
+__global__ void sp_disjoint_kernel(const int64_t* __restrict__ colptr, int ncols, int B, int* __restrict__ err) {
+  for (int64_t b = 1 + (int64_t)blockIdx.x * blockDim.x + threadIdx.x; b < B; b += (int64_t)gridDim.x * blockDim.x)
+    if (colptr[b * (ncols + 1)] < colptr[b * (ncols + 1) - 1]) atomicOr(err, 8);
+}
+
 // s = G z − h per problem, each row in Julia's `mul!` order for a
 // SparseMatrixCSC (column by column, product and sum rounded separately — the
 // oracle's gz_minus_h), from the CSR copy (columns ascending within a row)
@@ -330,6 +338,129 @@ __global__ __launch_bounds__(SP_TPB) void sp_lsqr_kernel(SpSys S, int B, int dir
   }
 }
 
+// ---- `_csc` calls: sparse tangents in, gradients sampled on a pattern out ------
+// The tangents dQ (n rows), dG (m), dA (p) staged like the model's matrices,
+// each with its own pattern (the reference's `sparse(I, J, V)`,
+// QuadraticProgram.jl:429-433) or absent.
+struct SpTan {
+  SpMat Q, G, A;
+  bool hasQ, hasG, hasA;
+};
+
+// forward RHS as sp_fwd_rhs_kernel, the dense tangents replaced by staged
+// sparse ones, with that kernel's sums in its own order: (dQ z)_j, (dG z)_i and
+// (dA z)_k by one thread walking the CSR row (columns ascending), (dGᵀλ + dAᵀν)_j
+// by a wave per column whose lanes hold that kernel's per-lane partial sums
+// (sparse_col_lane_sum over dG's CSC column, then dA's), and the same dq / dh /
+// db epilogue.  So the right-hand side — and with it the LSQR run — is
+// bit-identical to the dense-tangent call's on the densified tangents (finite
+// z, λ, ν; tangents without duplicate entries, rows sorted within a column):
+// two LSQR runs from right-hand sides that differ in the last bits can stop an
+// iteration apart and then agree only to ≈ 1e-7.  A staging error (*err != 0,
+// raised by the host after the call's wait) leaves every tangent unread.
+__global__ __launch_bounds__(SP_SETUP) void sp_fwd_rhs_csc_kernel(
+    SpTan T, const int* __restrict__ err, const double* __restrict__ dq, const double* __restrict__ dh,
+    const double* __restrict__ db, const double* __restrict__ z, const double* __restrict__ lam,
+    const double* __restrict__ nu, int n, int m, int p, double* __restrict__ rhs) {
+  const size_t b = blockIdx.x;
+  const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
+  const int L = n + m + p;
+  const bool ok = *err == 0;
+  const bool hQ = ok && T.hasQ, hG = ok && T.hasG && m, hA = ok && T.hasA && p;
+  const double* zb = z + b * n;
+  double* r = rhs + b * L;
+  // z block: dQ z + dq (thread per j), then dGᵀλ + dAᵀν (wave per j)
+  for (int j = t; j < n; j += SP_SETUP) {
+    double acc = 0.0;
+    if (hQ) {
+      const int64_t* rp = T.Q.rp + b * (n + 1);
+      for (int64_t k = rp[j]; k < rp[j + 1]; ++k) acc = fma(T.Q.rv[k], zb[T.Q.ci[k]], acc);
+    }
+    if (dq) acc += dq[b * n + j];
+    r[j] = acc;
+  }
+  __syncthreads();
+  if (hG || hA)
+    for (int j = wv; j < n; j += SP_SETUP / 64) {
+      double acc = 0.0;
+      if (hG) {
+        const int64_t* cp = T.G.cp + b * (n + 1);
+        acc = sparse_col_lane_sum(T.G.ri, T.G.cv, cp[j], cp[j + 1], lam + b * m, acc);
+      }
+      if (hA) {
+        const int64_t* cp = T.A.cp + b * (n + 1);
+        acc = sparse_col_lane_sum(T.A.ri, T.A.cv, cp[j], cp[j + 1], nu + b * p, acc);
+      }
+      acc = wave_sum(acc);
+      if (lane == 0) r[j] += acc;
+    }
+  // λ block: λ∘(dG z) − λ∘dh
+  for (int i = t; i < m; i += SP_SETUP) {
+    double acc = 0.0;
+    if (hG) {
+      const int64_t* rp = T.G.rp + b * (m + 1);
+      for (int64_t k = rp[i]; k < rp[i + 1]; ++k) acc = fma(T.G.rv[k], zb[T.G.ci[k]], acc);
+    }
+    const double l = lam[b * m + i];
+    r[n + i] = l * acc - (dh ? l * dh[b * m + i] : 0.0);
+  }
+  // ν block: dA z − db
+  for (int k0 = t; k0 < p; k0 += SP_SETUP) {
+    double acc = 0.0;
+    if (hA) {
+      const int64_t* rp = T.A.rp + b * (p + 1);
+      for (int64_t k = rp[k0]; k < rp[k0 + 1]; ++k) acc = fma(T.A.rv[k], zb[T.A.ci[k]], acc);
+    }
+    r[n + m + k0] = acc - (db ? db[b * p + k0] : 0.0);
+  }
+}
+
+// Reverse gradients at the entries of a pattern (the reference's lazy getters
+// read at the requested entries, QuadraticProgram.jl:461-473): grid (column
+// chunk, problem) as sp_conv_kernel — the column from the loop, the row from
+// rowval, one entry per thread, lanes over consecutive k; an entry index no
+// problem's range covers is left untouched.  `base` = 1 for a caller's Julia
+// arrays (validated here, error bits as sp_conv_kernel), 0 for the handle's
+// own staged pattern.  which: 0 dQ, 1 dG, 2 dA.  The entry expressions restate
+// qp_reverse_grads_kernel's (qp.hip) — change both together.
+template <class RT>
+__global__ __launch_bounds__(SP_SETUP) void sp_grads_at_kernel(
+    int which, const double* __restrict__ rev, const double* __restrict__ z, const double* __restrict__ lam,
+    const double* __restrict__ nu, int n, int m, int p, int B, const int64_t* __restrict__ colptr,
+    const RT* __restrict__ rowval, int base, int64_t nnz, double* __restrict__ out, int* __restrict__ err) {
+  const int L = n + m + p;
+  const int rows = which == 0 ? n : which == 1 ? m : p;
+  for (int b = blockIdx.y; b < B; b += gridDim.y) {
+    const int64_t* cp = colptr + (size_t)b * (n + 1);
+    const double* rb = rev + (size_t)b * L;
+    const double* zb = z + (size_t)b * n;
+    for (int j = blockIdx.x; j < n; j += gridDim.x) {
+      const int64_t k0 = cp[j] - base, k1 = cp[j + 1] - base;
+      if (k0 < 0 || k1 < k0 || k1 > nnz) {
+        if (threadIdx.x == 0) atomicOr(err, 1);
+        continue;
+      }
+      for (int64_t k = k0 + threadIdx.x; k < k1; k += SP_SETUP) {
+        const int64_t i = (int64_t)rowval[k] - base;
+        if (i < 0 || i >= rows) {
+          atomicOr(err, 2);
+          continue;
+        }
+        double v;
+        if (which == 0) {
+          v = 0.5 * (rb[i] * zb[j] + zb[i] * rb[j]);
+        } else if (which == 1) {
+          const double li = lam[(size_t)b * m + i];
+          v = li * rb[n + i] * zb[j] + li * rb[j];
+        } else {
+          v = rb[n + m + i] * zb[j] + nu[(size_t)b * p + i] * rb[j];
+        }
+        out[k] = v;
+      }
+    }
+  }
+}
+
 int grid1(int64_t work, int tpb) { return (int)std::max<int64_t>(1, std::min<int64_t>((work + tpb - 1) / tpb, 8192)); }
 
 }  // namespace
@@ -337,12 +468,18 @@ int grid1(int64_t work, int tpb) { return (int)std::max<int64_t>(1, std::min<int
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-// One matrix (slot 0: G, 1: A) of dopt_qp_set_csc: convert, validate, build
+// One matrix into `st` (h.sp: G and A of dopt_qp_set_csc, A_moi of
+// dopt_conic_set_csc; h.spt: a `_csc` call's tangent): convert, validate, build
 // the CSR copy.  `err` collects the error bits on the device.
-void sp_stage(Handle& h, int slot, const int64_t* colptr, const int64_t* rowval, const double* nzval,
-                     int64_t nnz, int rows, int* err) {
+void sp_stage(Handle& h, SpStore& st, const int64_t* colptr, const int64_t* rowval, const double* nzval,
+              int64_t nnz, int rows, int* err, bool disjoint) {
   const int B = (int)h.batch, n = h.n;
-  SpStore& st = h.sp[slot];
+  if (disjoint && nnz > INT32_MAX) throw Error(-1, "a sparse tangent holds at most 2^31 - 1 entries per batch");
+  if (disjoint && B > 1) {
+    hipLaunchKernelGGL(sp_disjoint_kernel, dim3(grid1(B - 1, SP_SETUP)), dim3(SP_SETUP), 0, h.stream, colptr, n, B,
+                       err);
+    DOPT_CHECK_HIP(hipGetLastError());
+  }
   st.nnz = nnz;
   st.rows = rows;
   st.cv = nzval;
@@ -396,8 +533,8 @@ void sp_set_csc(Handle& h, const int64_t* Qcp, const int64_t* Qrv, const double*
     hipLaunchKernelGGL(sp_qtest_kernel, dim3(grid1(Qnnz, SP_SETUP)), dim3(SP_SETUP), 0, h.stream, Qnz, Qnnz, err);
     DOPT_CHECK_HIP(hipGetLastError());
   }
-  if (h.m) sp_stage(h, 0, Gcp, Grv, Gnz, Gnnz, h.m, err);
-  if (h.p) sp_stage(h, 1, Acp, Arv, Anz, Annz, h.p, err);
+  if (h.m) sp_stage(h, h.sp[0], Gcp, Grv, Gnz, Gnnz, h.m, err);
+  if (h.p) sp_stage(h, h.sp[1], Acp, Arv, Anz, Annz, h.p, err);
 }
 
 static SpSys sp_sys(Handle& h) {
@@ -489,6 +626,79 @@ static void sp_fwd_rhs(Handle& h, const FwdTangents& T, double* r) {
                      h.m ? T.dG : nullptr, h.m ? T.dh : nullptr, h.p ? T.dA : nullptr, h.p ? T.db : nullptr, h.z,
                      h.m ? h.lam : &zd, h.p ? h.nu : &zd, h.n, h.m, h.p, r);
   DOPT_CHECK_HIP(hipGetLastError());
+}
+
+const char* sp_err_message(int err) {
+  if (err & 1) return "CSC colptr is not monotone / out of range";
+  if (err & 2) return "CSC rowval out of range";
+  if (err & 8) return "CSC colptr: the problems' entry ranges must be ascending and disjoint";
+  return nullptr;
+}
+
+static SpMat sp_mat(const SpStore& st) {
+  return SpMat{st.cp.as<int64_t>(), st.ri.as<int32_t>(), st.cv,          st.rp.as<int64_t>(),
+               st.ci.as<int32_t>(), st.rv.as<double>(),  st.rows};
+}
+
+// Stages the present tangents of a `_csc` call into h.spt (per call: the
+// model's h.sp is not touched) and writes the forward right-hand side from them
+static void sp_fwd_rhs_csc(Handle& h, const CscArg* T, const double* dq, const double* dh, const double* db,
+                           int* err, double* r) {
+  const int B = (int)h.batch;
+  const int rows[3] = {h.n, h.m, h.p};
+  PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
+  SpTan S{};
+  SpMat* mats[3] = {&S.Q, &S.G, &S.A};
+  bool* has[3] = {&S.hasQ, &S.hasG, &S.hasA};
+  for (int k = 0; k < 3; ++k) {
+    if (!T[k].cp || rows[k] == 0) continue;
+    sp_stage(h, h.spt[k], T[k].cp, T[k].rv ? T[k].rv : T[k].cp, T[k].nz, T[k].nnz, rows[k], err, true);
+    *mats[k] = sp_mat(h.spt[k]);
+    *has[k] = true;
+  }
+  hipLaunchKernelGGL(sp_fwd_rhs_csc_kernel, dim3((unsigned)B), dim3(SP_SETUP), 0, h.stream, S, err, dq,
+                     h.m ? dh : nullptr, h.p ? db : nullptr, h.z, h.lam, h.nu, h.n, h.m, h.p, r);
+  DOPT_CHECK_HIP(hipGetLastError());
+}
+
+void sp_forward_csc(Handle& h, const CscArg* T, const double* dq, const double* dh, const double* db, double* out,
+                    int* err) {
+  if (!h.factored) sp_factor(h);
+  double* r = sp_rhs(h, 1);
+  sp_fwd_rhs_csc(h, T, dq, dh, db, err, r);
+  sp_lsqr(h, 1, 1, 1, r, r, out, out);
+}
+
+void sp_forward_reverse_csc(Handle& h, const double* dl_dz, const CscArg* T, const double* dq, const double* dh,
+                            const double* db, double* out_rev, double* out_fwd, int* err) {
+  if (!h.factored) sp_factor(h);
+  double* rr = sp_rhs(h, 0);
+  double* rf = sp_rhs(h, 1);
+  sp_rev_rhs(h, dl_dz, rr);
+  sp_fwd_rhs_csc(h, T, dq, dh, db, err, rf);
+  sp_lsqr(h, 2, 0, 1, rr, rf, out_rev, out_fwd);
+}
+
+void sp_reverse_grads_at(Handle& h, const double* rev, const CscArg* P, double* const* out, int* err) {
+  if (!h.set) throw Error(-1, "dopt_qp_reverse_grads_csc: dopt_qp_set_csc has not been called");
+  const int B = (int)h.batch, n = h.n;
+  const int rows[3] = {h.n, h.m, h.p};
+  const int gx = std::max(1, std::min(n, 1024));
+  const int gy = std::min(B, 65535);
+  PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
+  for (int k = 0; k < 3; ++k) {
+    if (!out[k] || rows[k] == 0) continue;
+    if (P[k].cp) {
+      hipLaunchKernelGGL(sp_grads_at_kernel<int64_t>, dim3(gx, gy), dim3(SP_SETUP), 0, h.stream, k, rev, h.z, h.lam,
+                         h.nu, n, h.m, h.p, B, P[k].cp, P[k].rv ? P[k].rv : P[k].cp, 1, P[k].nnz, out[k], err);
+    } else {   // the handle's own G / A, as staged (0-based)
+      if (k == 0) throw Error(-1, "dopt_qp_reverse_grads_csc: the sparse route keeps no Q pattern; pass one");
+      const SpStore& st = h.sp[k - 1];
+      hipLaunchKernelGGL(sp_grads_at_kernel<int32_t>, dim3(gx, gy), dim3(SP_SETUP), 0, h.stream, k, rev, h.z, h.lam,
+                         h.nu, n, h.m, h.p, B, st.cp.as<int64_t>(), st.ri.as<int32_t>(), 0, st.nnz, out[k], err);
+    }
+    DOPT_CHECK_HIP(hipGetLastError());
+  }
 }
 
 void sp_reverse(Handle& h, const double* dl_dz, double* out) {

@@ -42,6 +42,67 @@ def vector(x, shape):
     return np.ascontiguousarray(np.asarray(x, dtype=np.float64).reshape(shape))
 
 
+def is_sparse(x):
+    """scipy.sparse matrix, or a list / tuple of them (a batch of sparse tangents)."""
+    if x is None or _is_torch(x) or isinstance(x, np.ndarray):
+        return False
+    import scipy.sparse as sp
+    if sp.issparse(x):
+        return True
+    return isinstance(x, (list, tuple)) and len(x) > 0 and all(sp.issparse(M) for M in x)
+
+
+def csc_pack(mats, B, shape):
+    """Batch of scipy-sparse matrices → the ABI's batched Julia CSC arrays
+    ``(colptr, rowval, nzval, nnz)``: int64, 1-based; problem b's colptr is
+    ``colptr[b*(ncols+1):(b+1)*(ncols+1)]`` and indexes the concatenated
+    rowval / nzval (running offsets, so the problems' ranges are ascending and
+    disjoint — a shared matrix is replicated).  Each matrix is canonicalised on
+    a copy (duplicates summed, row indices sorted; the caller's is not
+    modified); the values of problem b are
+    ``nzval[colptr[b*(ncols+1)]-1 : colptr[(b+1)*(ncols+1)-1]-1]`` in that
+    matrix's canonical CSC order.  ValueError on a shape mismatch."""
+    import scipy.sparse as sp
+    mats = [mats] * B if sp.issparse(mats) else list(mats)
+    if len(mats) != B:
+        raise ValueError(f"{len(mats)} sparse matrices for a batch of {B}")
+    cps, rvs, nzs, off = [], [], [], 0
+    for M in mats:
+        if tuple(M.shape) != tuple(shape):
+            raise ValueError(f"sparse matrix of shape {tuple(M.shape)}, expected {tuple(shape)}")
+        M = sp.csc_matrix(M, dtype=np.float64, copy=True)
+        M.sum_duplicates()
+        M.sort_indices()
+        cps.append(M.indptr.astype(np.int64) + (off + 1))
+        rvs.append(M.indices.astype(np.int64) + 1)
+        nzs.append(M.data.astype(np.float64))
+        off += int(M.nnz)
+    ncols = int(shape[1])
+    colptr = np.ascontiguousarray(np.concatenate(cps)) if cps else np.zeros(0, dtype=np.int64)
+    assert colptr.size == B * (ncols + 1)
+    rowval = np.ascontiguousarray(np.concatenate(rvs)) if cps else np.zeros(0, dtype=np.int64)
+    nzval = np.ascontiguousarray(np.concatenate(nzs)) if cps else np.zeros(0, dtype=np.float64)
+    return colptr, rowval, nzval, off
+
+
+def csc_args(packed, values=True):
+    """ctypes arguments of one packed matrix (``None``: absent): colptr,
+    rowval, [nzval,] nnz, with NULL rowval / nzval for nnz == 0."""
+    if packed is None:
+        return [None, None, None, 0] if values else [None, None, 0]
+    cp, rv, nz, nnz = packed
+    a = [cp.ctypes.data, rv.ctypes.data if nnz else None]
+    if values:
+        a.append(nz.ctypes.data if nnz else None)
+    return a + [nnz]
+
+
+def csc_split(values, packed, B, ncols):
+    """Per-problem views of a packed value array: a list of B arrays."""
+    cp = packed[0]
+    return [values[cp[b * (ncols + 1)] - 1: cp[(b + 1) * (ncols + 1) - 1] - 1].copy() for b in range(B)]
+
+
 class Staged:
     """Decides host vs device mode for one ABI call and yields raw pointers."""
 

@@ -55,6 +55,20 @@ SIGNATURES = {
                                               ctypes.c_int64] * 3 + [ctypes.c_void_p] * 4),
     "dopt_qp_forward": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 7),
     "dopt_qp_forward_reverse": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 9),
+    # the `_csc` calls: a tangent is (colptr, rowval, nzval, nnz), a pattern (colptr, rowval, nnz)
+    "dopt_qp_forward_csc": (ctypes.c_int, [_h] + ([ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p]) * 3
+                            + [ctypes.c_void_p]),
+    "dopt_qp_forward_reverse_csc": (ctypes.c_int, [_h, ctypes.c_void_p]
+                                    + ([ctypes.c_void_p] * 3 + [ctypes.c_int64, ctypes.c_void_p]) * 3
+                                    + [ctypes.c_void_p] * 2),
+    "dopt_qp_reverse_grads_csc": (ctypes.c_int, [_h, ctypes.c_void_p]
+                                  + [ctypes.c_void_p, ctypes.c_void_p, ctypes.c_int64, ctypes.c_void_p] * 3),
+    "dopt_conic_forward_csc": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 3 + [ctypes.c_int64]
+                               + [ctypes.c_void_p] * 4),
+    "dopt_conic_forward_reverse_csc": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 3 + [ctypes.c_int64]
+                                       + [ctypes.c_void_p] * 8),
+    "dopt_conic_reverse_grads_csc": (ctypes.c_int, [_h, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
+                                                    ctypes.c_int64, ctypes.c_void_p]),
     "dopt_qp_reverse_k": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_void_p, ctypes.c_void_p]),
     "dopt_qp_forward_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 7),
     "dopt_conic_forward_reverse": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 10),

@@ -18,7 +18,7 @@ import time
 import numpy as np
 
 from . import _lib
-from ._arrays import Staged, colmajor, vector
+from ._arrays import Staged, colmajor, csc_args, csc_pack, csc_split, is_sparse, vector
 
 ZEROS, NONNEG, NONPOS, SOC, PSD = (_lib.CONE_ZEROS, _lib.CONE_NONNEG, _lib.CONE_NONPOS,
                                    _lib.CONE_SOC, _lib.CONE_PSD_TRI)
@@ -68,6 +68,7 @@ class ConicBatch:
     def set(self, A, b, c, x, s, y):
         """``A``: (B, m, n) MOI coefficients; ``c`` already sign-adjusted for MAX."""
         B, n, m = self.batch, self.n, self.m
+        self._own_csc = None
         st = self._stage([A, b, c, x, s, y])
         args = [colmajor(A, (B, m, n)), vector(b, (B, m)), vector(c, (B, n)),
                 vector(x, (B, n)), vector(s, (B, m)), vector(y, (B, m))]
@@ -96,6 +97,7 @@ class ConicBatch:
         cp = np.ascontiguousarray(np.concatenate(cps))
         rv = np.ascontiguousarray(np.concatenate(rvs))
         nz = np.ascontiguousarray(np.concatenate(nzs))
+        self._own_csc = None
         st = self._stage([b, c, x, s, y])
         if st.mem != _lib.DOPT_MEM_HOST:
             raise TypeError("set_csc takes host (numpy / scipy) arrays")
@@ -107,13 +109,19 @@ class ConicBatch:
                                          *[st.ptr(v) for v in vecs],
                                          desc.ctypes.data if desc.size else None, len(self.cones))
         _lib.check(rc, self.h)
+        self._own_csc = (cp, rv, nz, off)   # the colptr reverse_grads_at(pattern=None) splits its values by
 
     def factor(self):
         _lib.check(self.lib.dopt_conic_factor(self.h), self.h)
 
     def forward(self, dA=None, db=None, dc=None):
-        """Returns (out (B, N) = [du | dv | dw], dx (B, n) = ForwardVariablePrimal)."""
+        """Returns (out (B, N) = [du | dv | dw], dx (B, n) = ForwardVariablePrimal).
+        ``dA``: dense (B, m, n), or scipy-sparse (one shared matrix or a list of
+        B) with its own pattern — then dopt_conic_forward_csc, no dense m × n
+        array anywhere."""
         B, n, m = self.batch, self.n, self.m
+        if is_sparse(dA):
+            return self._forward_csc(dA, db, dc)
         st = self._stage([dA, db, dc])
         dev = st.mem == _lib.DOPT_MEM_DEVICE
         args = [colmajor(dA, (B, m, n)) if dA is not None else None,
@@ -124,6 +132,48 @@ class ConicBatch:
         rc = self.lib.dopt_conic_forward(self.h, *[st.ptr(a) for a in args], st.ptr(out), st.ptr(dx))
         _lib.check(rc, self.h)
         return out, dx
+
+    def _forward_csc(self, dA, db, dc):
+        B, n, m = self.batch, self.n, self.m
+        st = self._stage([db, dc])
+        if st.mem != _lib.DOPT_MEM_HOST:
+            raise TypeError("a scipy-sparse dA goes with host (numpy) db / dc")
+        packed = csc_pack(dA, B, (m, n))
+        vecs = [vector(db, (B, m)) if db is not None else None,
+                vector(dc, (B, n)) if dc is not None else None]
+        out = Staged.empty((B, self.N), False)
+        dx = Staged.empty((B, n), False)
+        rc = self.lib.dopt_conic_forward_csc(self.h, *csc_args(packed), *[st.ptr(a) for a in vecs],
+                                             st.ptr(out), st.ptr(dx))
+        _lib.check(rc, self.h)
+        return out, dx
+
+    def reverse_grads_at(self, g, pattern=None):
+        """The reverse gradient dA read at the entries of a pattern
+        (dopt_conic_reverse_grads_csc; the reference's lazy ``_get_dA``):
+        ``g`` (B, N) is a reverse call's first output; ``pattern`` is one
+        scipy-sparse m × n matrix or a list of B (only the patterns are used),
+        ``None`` = the pattern the handle got from ``set_csc`` (sparse-route
+        handles).  Returns a list of B value arrays, problem b's aligned with
+        its pattern's canonical CSC order (duplicates summed, rows sorted):
+        ``values[k] = g[n+i]·x[j] − vp[i]·g[j]`` for entry k = (i, j)."""
+        B, n, m = self.batch, self.n, self.m
+        st = self._stage([g])
+        if st.mem != _lib.DOPT_MEM_HOST:
+            raise TypeError("reverse_grads_at takes a host (numpy) g")
+        gv = vector(g, (B, self.N))
+        if pattern is None:
+            cnt = getattr(self, "_own_csc", None)
+            if cnt is None:
+                raise _lib.EngineError(-1, "reverse_grads_at(pattern=None) needs a model given by set_csc")
+            packed, args = cnt, [None, None, 0]
+        else:
+            packed = csc_pack(pattern, B, (m, n))
+            args = csc_args(packed, values=False)
+        out = np.zeros(max(packed[3], 1), dtype=np.float64)
+        rc = self.lib.dopt_conic_reverse_grads_csc(self.h, st.ptr(gv), *args, out.ctypes.data)
+        _lib.check(rc, self.h)
+        return csc_split(out, packed, B, n)
 
     def reverse(self, dx, want_dA=True):
         """Returns (g (B, N), dA (B, m, n) | None, db (B, m), dc (B, n))."""
@@ -145,8 +195,25 @@ class ConicBatch:
     def forward_reverse(self, dx, dA=None, db=None, dc=None, want_dA=True):
         """Both directions in one call, the two LSQR runs co-iterated
         (dopt_conic_forward_reverse): ((out, dx_fwd), (g, dA, db, dc)) as
-        ``forward`` / ``reverse`` return them, bit-identical to those calls."""
+        ``forward`` / ``reverse`` return them, bit-identical to those calls.
+        A scipy-sparse ``dA`` (see ``forward``) goes to
+        dopt_conic_forward_reverse_csc, which has no dense gradient: the
+        reverse tuple's dA is ``None`` (read it with ``reverse_grads_at``)."""
         B, n, m = self.batch, self.n, self.m
+        if is_sparse(dA):
+            st = self._stage([db, dc, dx])
+            if st.mem != _lib.DOPT_MEM_HOST:
+                raise TypeError("a scipy-sparse dA goes with host (numpy) db / dc / dx")
+            packed = csc_pack(dA, B, (m, n))
+            vecs = [vector(db, (B, m)) if db is not None else None,
+                    vector(dc, (B, n)) if dc is not None else None, vector(dx, (B, n))]
+            out, fdx, g = (Staged.empty(s_, False) for s_ in ((B, self.N), (B, n), (B, self.N)))
+            rb, rc_ = Staged.empty((B, m), False), Staged.empty((B, n), False)
+            rc = self.lib.dopt_conic_forward_reverse_csc(self.h, *csc_args(packed), *[st.ptr(a) for a in vecs],
+                                                         st.ptr(out), st.ptr(fdx), st.ptr(g), st.ptr(rb),
+                                                         st.ptr(rc_))
+            _lib.check(rc, self.h)
+            return (out, fdx), (g, None, rb, rc_)
         st = self._stage([dA, db, dc, dx])
         dev = st.mem == _lib.DOPT_MEM_DEVICE
         args = [colmajor(dA, (B, m, n)) if dA is not None else None,

@@ -20,7 +20,7 @@ import ctypes
 import numpy as np
 
 from . import _lib
-from ._arrays import Staged, colmajor, vector
+from ._arrays import Staged, colmajor, csc_args, csc_pack, csc_split, is_sparse, vector
 from ._arrays import _is_torch as _is_t
 
 LE, EQ = "LessThan", "EqualTo"
@@ -167,9 +167,40 @@ class QPBatch:
         _lib.check(rc, self.h, singular_ok)
         return out
 
+    def _csc_tangents(self, dQ, dq, dG, dh, dA, db, extra=()):
+        """The `_csc` calls' tangent arguments: scipy-sparse dQ / dG / dA (one
+        shared matrix or a list of B, each with its own pattern; None = zero)
+        packed, the vector tangents staged.  Returns (st, ctypes args, keep)."""
+        B, n, m, p = self.batch, self.n, self.m, self.p
+        for M in (dQ, dG, dA):
+            if M is not None and not is_sparse(M):
+                raise TypeError("dQ, dG and dA must all be scipy-sparse (or None) when one of them is")
+        st = self._stage([dq, dh, db, *extra])
+        if st.mem != _lib.DOPT_MEM_HOST:
+            raise TypeError("scipy-sparse tangents go with host (numpy) vector tangents")
+        packs = [csc_pack(dQ, B, (n, n)) if dQ is not None else None,
+                 csc_pack(dG, B, (m, n)) if (dG is not None and m) else None,
+                 csc_pack(dA, B, (p, n)) if (dA is not None and p) else None]
+        vecs = [vector(dq, (B, n)) if dq is not None else None,
+                vector(dh, (B, m)) if (dh is not None and m) else None,
+                vector(db, (B, p)) if (db is not None and p) else None]
+        args = []
+        for pk, v in zip(packs, vecs):
+            args += csc_args(pk) + [st.ptr(v)]
+        return st, args, (packs, vecs)
+
     def forward(self, dQ=None, dq=None, dG=None, dh=None, dA=None, db=None,
                 singular_ok=False):
+        """``dQ`` / ``dG`` / ``dA``: dense (B, rows, n) arrays, or — on a
+        sparse-route handle — scipy-sparse matrices with their own patterns
+        (dopt_qp_forward_csc: no dense rows × n array anywhere)."""
         B, n, m, p = self.batch, self.n, self.m, self.p
+        if any(is_sparse(M) for M in (dQ, dG, dA)):
+            st, args, keep = self._csc_tangents(dQ, dq, dG, dh, dA, db)
+            out = self._out(False)
+            rc = self.lib.dopt_qp_forward_csc(self.h, *args, st.ptr(out))
+            _lib.check(rc, self.h, singular_ok)
+            return out
         st = self._stage([dQ, dq, dG, dh, dA, db])
         args = [colmajor(dQ, (B, n, n)) if dQ is not None else None,
                 vector(dq, (B, n)) if dq is not None else None,
@@ -218,8 +249,20 @@ class QPBatch:
 
     def forward_reverse(self, dl_dz, dQ=None, dq=None, dG=None, dh=None, dA=None,
                         db=None, out_rev=None, out_fwd=None, singular_ok=False):
-        """One full sensitivity solve per problem: factor + reverse + forward."""
+        """One full sensitivity solve per problem: factor + reverse + forward.
+        scipy-sparse ``dQ`` / ``dG`` / ``dA`` as in ``forward``
+        (dopt_qp_forward_reverse_csc)."""
         B, n, m, p = self.batch, self.n, self.m, self.p
+        if any(is_sparse(M) for M in (dQ, dG, dA)):
+            st, args, keep = self._csc_tangents(dQ, dq, dG, dh, dA, db, extra=(dl_dz,))
+            o1 = out_rev if out_rev is not None else self._out(False)
+            o2 = out_fwd if out_fwd is not None else self._out(False)
+            for o in (o1, o2):
+                _check_out(o, (B, self.L), False)
+            d = vector(dl_dz, (B, n))
+            rc = self.lib.dopt_qp_forward_reverse_csc(self.h, st.ptr(d), *args, st.ptr(o1), st.ptr(o2))
+            _lib.check(rc, self.h, singular_ok)
+            return o1, o2
         st = self._stage([dl_dz, dQ, dq, dG, dh, dA, db])
         dev = st.mem == _lib.DOPT_MEM_DEVICE
         args = [vector(dl_dz, (B, n)),
@@ -306,6 +349,45 @@ class QPBatch:
             if out[k] is not None:
                 out[k] = out[k].transpose(1, 2) if _is_t(out[k]) else np.swapaxes(out[k], 1, 2)
         return out
+
+    def reverse_grads_at(self, rev, G=None, A=None, Q=None):
+        """``reverse_grads``' matrix gradients read at the entries of patterns
+        (dopt_qp_reverse_grads_csc, sparse-route handles; the reference's lazy
+        getters, QuadraticProgram.jl:461-473) — no dense rows × n array.
+        ``G`` / ``A`` / ``Q``: scipy-sparse patterns (one shared or a list of
+        B); ``None`` for G / A = the pattern the handle got from ``set_csc``,
+        for Q = skipped.  Returns a dict of lists of B value arrays ("dG",
+        "dA", and "dQ" when asked), problem b's aligned with its pattern's
+        canonical CSC order (a given pattern: duplicates summed, rows sorted;
+        the handle's own: the order ``set_csc`` passed)."""
+        B, n, m, p = self.batch, self.n, self.m, self.p
+        st = self._stage([rev])
+        if st.mem != _lib.DOPT_MEM_HOST:
+            raise TypeError("reverse_grads_at takes a host (numpy) rev")
+        r = vector(rev, (B, self.L))
+        own = getattr(self, "_csc_keep", (None, None))[0]
+
+        def pick(pat, rows, slot):
+            if rows == 0 or (pat is None and slot == 0):
+                return None, [None, None, 0], None
+            if pat is not None:
+                pk = csc_pack(pat, B, (rows, n))
+                return pk, csc_args(pk, values=False), np.zeros(max(pk[3], 1))
+            if own is None or own[slot][0] is None:
+                raise _lib.EngineError(-1, "reverse_grads_at: no pattern given and none kept from set_csc")
+            return own[slot], [None, None, 0], np.zeros(max(own[slot][3], 1))
+
+        picks = [pick(Q, n, 0), pick(G, m, 1), pick(A, p, 2)]
+        args = []
+        for pk, a, out in picks:
+            args += a + [out.ctypes.data if out is not None else None]
+        rc = self.lib.dopt_qp_reverse_grads_csc(self.h, st.ptr(r), *args)
+        _lib.check(rc, self.h)
+        res = {}
+        for key, (pk, a, out) in zip(("dQ", "dG", "dA"), picks):
+            if out is not None:
+                res[key] = csc_split(out, pk, B, n)
+        return res
 
     # ---- introspection -----------------------------------------------------
     def info(self):

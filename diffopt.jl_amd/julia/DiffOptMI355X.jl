@@ -38,6 +38,7 @@ mutable struct Handle
     n::Int
     m::Int
     p::Int
+    sparse::Bool   # the handle is on the sparse route (dopt_set_sparse, or a QP above the dense cap)
 end
 
 function _check(rc::Cint, ptr::Ptr{Cvoid})
@@ -53,7 +54,8 @@ function Handle(n::Int, m::Int, p::Int; device::Integer = 0, kind::Int32 = KIND_
                (Ptr{Ptr{Cvoid}}, Cint, Int64, Int32, Int32, Int32, Int32),
                r, device, 1, n, m, p, kind)
     _check(rc, r[])
-    h = Handle(r[], n, m, p)
+    # a QP handle with n + m + p > 8192 takes the sparse route by itself (include/diffopt_mi355x.h)
+    h = Handle(r[], n, m, p, kind == KIND_QP && n + m + p > 8192)
     finalizer(h) do hh
         hh.ptr == C_NULL || ccall((:dopt_destroy, LIB), Cint, (Ptr{Cvoid},), hh.ptr)
         hh.ptr = C_NULL
@@ -201,7 +203,6 @@ function DiffOpt.forward_differentiate!(m::QPModel)
         n, mi, p = h.n, h.m, h.p
         f = DiffOpt._convert(MOI.ScalarQuadraticFunction{Float64}, m.input_cache.objective)
         sa = DiffOpt.sparse_array_representation(f, n)
-        dQ = Matrix{Float64}(sa.quadratic_terms)
         dq = Vector{Float64}(sa.affine_terms)
         sets = QP._QPSets()
         db = zeros(p)
@@ -213,18 +214,41 @@ function DiffOpt.forward_differentiate!(m::QPModel)
         I, J, V = Int[], Int[], Float64[]
         DiffOpt._fill(isequal(MOI.EqualTo{Float64}), isequal(MOI.GreaterThan{Float64}),
                       nothing, m.input_cache, sets, I, J, V)
-        dA = Matrix{Float64}(SparseArrays.sparse(I, J, V, p, n))
+        sdA = SparseArrays.sparse(I, J, V, p, n)
         I, J, V = Int[], Int[], Float64[]
         DiffOpt._fill(!isequal(MOI.EqualTo{Float64}), isequal(MOI.GreaterThan{Float64}),
                       nothing, m.input_cache, sets, I, J, V)
-        dG = Matrix{Float64}(SparseArrays.sparse(I, J, V, mi, n))
+        sdG = SparseArrays.sparse(I, J, V, mi, n)
         out = Vector{Float64}(undef, n + mi + p)
-        GC.@preserve dQ dq dG dh dA db begin
-            _check(ccall((:dopt_qp_forward, LIB), Cint,
-                         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
-                          Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-                         h.ptr, _ptr(dQ), _ptr(dq), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
-                         out), h.ptr)
+        if h.sparse
+            # sparse route: the tangents stay `sparse(I, J, V)` with their own
+            # patterns, as in the reference (QuadraticProgram.jl:429-433) — no
+            # dense rows × n array (dopt_qp_forward_csc).  NOT EXECUTED: the
+            # project's test environment has no Julia; the Python tests exercise the entry.
+            sdQ = SparseArrays.SparseMatrixCSC{Float64,Int64}(sa.quadratic_terms)
+            sdG = SparseArrays.SparseMatrixCSC{Float64,Int64}(sdG)
+            sdA = SparseArrays.SparseMatrixCSC{Float64,Int64}(sdA)
+            GC.@preserve sdQ dq sdG dh sdA db begin
+                _check(ccall((:dopt_qp_forward_csc, LIB), Cint,
+                             (Ptr{Cvoid},
+                              Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64},
+                              Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64},
+                              Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64},
+                              Ptr{Float64}),
+                             h.ptr, _csc(sdQ)..., _ptr(dq), _csc(sdG)..., _ptr(dh), _csc(sdA)..., _ptr(db),
+                             out), h.ptr)
+            end
+        else
+            dQ = Matrix{Float64}(sa.quadratic_terms)
+            dA = Matrix{Float64}(sdA)
+            dG = Matrix{Float64}(sdG)
+            GC.@preserve dQ dq dG dh dA db begin
+                _check(ccall((:dopt_qp_forward, LIB), Cint,
+                             (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64},
+                              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             h.ptr, _ptr(dQ), _ptr(dq), _ptr(dG), _ptr(dh), _ptr(dA), _ptr(db),
+                             out), h.ptr)
+            end
         end
         inner.forw_grad_cache = _split(out, n, mi)
     end
@@ -400,6 +424,7 @@ function _ensure!(m::ConicModel)
         # a SparseMatrixCSC, ConicProgram.jl:323, :372) instead of an m×n dense copy
         if mr * n > 4_000_000 && SparseArrays.nnz(Amoi) < 0.05 * mr * n && _sparse_cones_ok(desc)
             _check(ccall((:dopt_set_sparse, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, Int32(1)), h.ptr)
+            h.sparse = true
         end
     end
     key = (Amoi, b, c, copy(inner.x), copy(inner.s), copy(inner.y), desc)
@@ -435,12 +460,27 @@ function DiffOpt.forward_differentiate!(m::ConicModel)
         DiffOpt._fill(S -> false, nothing, m.input_cache, m.model.constraints.sets, db)
         I, J, V = Int[], Int[], Float64[]
         DiffOpt._fill(S -> false, nothing, m.input_cache, m.model.constraints.sets, I, J, V)
-        dA = Matrix{Float64}(SparseArrays.sparse(I, J, V, mr, n))
+        sdA = SparseArrays.SparseMatrixCSC{Float64,Int64}(SparseArrays.sparse(I, J, V, mr, n))
         out = Vector{Float64}(undef, n + mr + 1)
-        GC.@preserve dA db dc begin
-            _check(ccall((:dopt_conic_forward, LIB), Cint,
-                         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
-                         h.ptr, _ptr(dA), _ptr(db), _ptr(dc), out, Ptr{Float64}(C_NULL)), h.ptr)
+        if h.sparse
+            # sparse route (chosen by _ensure! because mr·n is large): dA stays
+            # the reference's `sparse(dAi, dAj, dAv, lines, cols)`
+            # (ConicProgram.jl:288-305) — dopt_conic_forward_csc, no dense mr × n
+            # array.  NOT EXECUTED: the project's test environment has no Julia; the
+            # Python tests exercise the entry.
+            GC.@preserve sdA db dc begin
+                _check(ccall((:dopt_conic_forward_csc, LIB), Cint,
+                             (Ptr{Cvoid}, Ptr{Int64}, Ptr{Int64}, Ptr{Float64}, Int64, Ptr{Float64},
+                              Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             h.ptr, _csc(sdA)..., _ptr(db), _ptr(dc), out, Ptr{Float64}(C_NULL)), h.ptr)
+            end
+        else
+            dA = Matrix{Float64}(sdA)
+            GC.@preserve dA db dc begin
+                _check(ccall((:dopt_conic_forward, LIB), Cint,
+                             (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             h.ptr, _ptr(dA), _ptr(db), _ptr(dc), out, Ptr{Float64}(C_NULL)), h.ptr)
+            end
         end
         inner.forw_grad_cache = CP.ForwCache(out[1:n], out[n+1:n+mr], [out[end]])
     end

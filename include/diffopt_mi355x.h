@@ -92,8 +92,10 @@ int dopt_qp_set(dopt_handle* h, const double* Q, const double* G,
 /* Sparse route (sparse.hip; on = 1).  CONIC handles: dopt_conic_set_csc keeps
  * A_moi as CSC plus a CSR copy (no dense m×n A) and every LSQR run applies M
  * matrix-free from them (ConicProgram.jl:243-247, :323, :372), one workgroup per
- * problem; PSD cones up to side 64; dopt_conic_set (dense) is refused; dense
- * tangents / dA outputs stay optional dense arrays (NULL = skip).
+ * problem; PSD cones up to side 64; dopt_conic_set (dense) is refused.  The
+ * matrix tangent and the matrix gradient have sparse forms on every conic
+ * route (dopt_conic_forward_csc, dopt_conic_reverse_grads_csc below); the dense
+ * dA / out_dA arguments of the other calls remain optional (NULL = skip).
  * QP handles (the sparse QP route).  The MOI matrix form stays sparse, as
  * in the reference (`_gradient_cache` keeps SparseMatrixCSC,
  * QuadraticProgram.jl:182-213): dopt_qp_set_csc keeps G and A as CSC plus a
@@ -106,7 +108,11 @@ int dopt_qp_set(dopt_handle* h, const double* Q, const double* G,
  * n + m + p > 8192 (the dense route's cap; on = 0 is then refused); opt-in
  * below it (tests compare the two routes).  Resets the handle's model.  Not on
  * this route: dopt_qp_set (dense inputs), the multi-RHS calls, the kept mask.
- * Forward tangents dQ / dG / dA stay dense column-major arrays (NULL = zero). */
+ * Matrix tangents and matrix gradients at the sizes this route exists for go
+ * through dopt_qp_forward_csc / dopt_qp_forward_reverse_csc /
+ * dopt_qp_reverse_grads_csc (sparse tangents with their own patterns, gradients
+ * sampled on a pattern); dopt_qp_forward's dense dQ / dG / dA still work here
+ * (NULL = zero) for problems small enough to hold them. */
 int dopt_set_sparse(dopt_handle* h, int32_t on);
 /* LSQR statistics of the sparse route's last solves, 4·B int32: per problem
  * [istop | iterations] of the reverse run, then of the forward run. */
@@ -209,6 +215,58 @@ int dopt_qp_forward_reverse(dopt_handle* h, const double* dl_dz,
                             const double* dA, const double* db,
                             double* out_rev, double* out_fwd);
 
+/* ---- sparse tangents and on-pattern gradients (`_csc` calls) -----------------
+ * The reference never densifies a matrix tangent or a matrix gradient: the
+ * forward tangent is `sparse(I, J, V, rows, cols)` and enters only through
+ * products (QuadraticProgram.jl:429-433; ConicProgram.jl:288-305, :314-318), and
+ * the reverse gradient is a lazy rank-2 expression read at the requested
+ * entries (QuadraticProgram.jl:461-473; ConicProgram.jl:430-443).  These calls do
+ * the same.  A tangent matrix `X csc` is the four arguments X_colptr, X_rowval,
+ * X_nzval, X_nnz in the convention of dopt_qp_set_csc: Julia
+ * SparseMatrixCSC{Float64,Int64} arrays, 1-based, problem b's colptr at
+ * X_colptr + b·(n+1), indexing the concatenated X_rowval / X_nzval; host mode
+ * copies, device mode borrows (for the duration of the call).  A tangent has
+ * ITS OWN pattern (the perturbation's, not the model's).  X_colptr == NULL: the
+ * tangent is absent (zero); X_nnz == 0 with NULL rowval / nzval is valid.  A
+ * pattern is colptr, rowval, nnz in the same convention.
+ * Validation: a malformed colptr or rowval returns −1 with a message, as in
+ * dopt_qp_set_csc; in addition the problems' entry ranges must be ascending
+ * and disjoint (cp_b[1] ≥ cp_{b−1}[n+1]).  The verdict is read with the call's
+ * final wait: after a −1 the outputs are unspecified, the handle's model is
+ * untouched and still solves.  The staged tangents live for one call only.
+ * The _k calls keep dense tangents.
+ *
+ * QP, sparse-route handles only (a dense-route handle returns −1 and names
+ * dopt_qp_forward / dopt_qp_forward_reverse / dopt_qp_reverse_grads):
+ * dopt_qp_forward with dQ (n×n), dG (m×n), dA (p×n) sparse. */
+int dopt_qp_forward_csc(dopt_handle* h,
+                        const int64_t* dQ_colptr, const int64_t* dQ_rowval, const double* dQ_nzval, int64_t dQ_nnz,
+                        const double* dq,
+                        const int64_t* dG_colptr, const int64_t* dG_rowval, const double* dG_nzval, int64_t dG_nnz,
+                        const double* dh,
+                        const int64_t* dA_colptr, const int64_t* dA_rowval, const double* dA_nzval, int64_t dA_nnz,
+                        const double* db, double* out);
+/* dopt_qp_forward_reverse with sparse dQ, dG, dA. */
+int dopt_qp_forward_reverse_csc(dopt_handle* h, const double* dl_dz,
+                                const int64_t* dQ_colptr, const int64_t* dQ_rowval, const double* dQ_nzval,
+                                int64_t dQ_nnz, const double* dq,
+                                const int64_t* dG_colptr, const int64_t* dG_rowval, const double* dG_nzval,
+                                int64_t dG_nnz, const double* dh,
+                                const int64_t* dA_colptr, const int64_t* dA_rowval, const double* dA_nzval,
+                                int64_t dA_nnz, const double* db, double* out_rev, double* out_fwd);
+/* dopt_qp_reverse_grads' matrix gradients read at the entries of a pattern:
+ * out_dX_nz[k] for entry k = (i, j) of problem b, in the pattern's order,
+ *   dQ_ij = (dz_i z_j + z_i dz_j)/2,  dG_ij = λ_i dλ_i z_j + λ_i dz_j,
+ *   dA_ij = dν_i z_j + ν_i dz_j.
+ * An output that is NULL is skipped.  A NULL G / A colptr with a non-NULL
+ * output means the pattern the handle got from dopt_qp_set_csc (out of G_nnz /
+ * A_nnz entries); Q's pattern is not kept and must be given.  An entry index no
+ * problem's column range covers is left untouched. */
+int dopt_qp_reverse_grads_csc(dopt_handle* h, const double* rev,
+                              const int64_t* Q_colptr, const int64_t* Q_rowval, int64_t Q_nnz, double* out_dQ_nz,
+                              const int64_t* G_colptr, const int64_t* G_rowval, int64_t G_nnz, double* out_dG_nz,
+                              const int64_t* A_colptr, const int64_t* A_rowval, int64_t A_nnz, double* out_dA_nz);
+
 /* ---- parameters (ParametricOptInterface glue, reference src/parameters.jl) ----
  * A parametric term t: t_param[t] ∈ [0, nparam), t_kind[t]:
  *   0  parameter term of LessThan row t_index[t]   (ParametricAffineFunction)
@@ -283,6 +341,31 @@ int dopt_conic_forward_reverse(dopt_handle* h, const double* dA, const double* d
                                const double* dc, const double* dx, double* out,
                                double* out_dx, double* out_g, double* out_dA,
                                double* out_db, double* out_dc);
+/* The `_csc` forms (conventions above, at dopt_qp_forward_csc), on EVERY conic
+ * route — the right-hand side does not depend on how LSQR runs.
+ * dopt_conic_forward with dA (m×n) as a sparse tangent with its own pattern:
+ * the right-hand side takes dAᵀvp and dA·x from the tangent's CSC / CSR copies,
+ * never from a dense m×n array.  A NULL colptr or an empty tangent gives
+ * dopt_conic_forward(dA = NULL)'s result bit for bit. */
+int dopt_conic_forward_csc(dopt_handle* h, const int64_t* dA_colptr, const int64_t* dA_rowval,
+                           const double* dA_nzval, int64_t dA_nnz, const double* db, const double* dc,
+                           double* out, double* out_dx);
+/* dopt_conic_forward_reverse with the sparse tangent; no dense out_dA (read
+ * the gradient with dopt_conic_reverse_grads_csc).  Bit-identical to
+ * dopt_conic_forward_csc plus dopt_conic_reverse. */
+int dopt_conic_forward_reverse_csc(dopt_handle* h, const int64_t* dA_colptr, const int64_t* dA_rowval,
+                                   const double* dA_nzval, int64_t dA_nnz, const double* db, const double* dc,
+                                   const double* dx, double* out, double* out_dx, double* out_g,
+                                   double* out_db, double* out_dc);
+/* The reverse gradient dA read at the entries of a pattern (`_get_dA`,
+ * ConicProgram.jl:430-443): g = a reverse call's out_g ((n+m+1)×B);
+ * out_nz[k] = g[n+i]·x[j] − vp[i]·g[j] for entry k = (i, j) of problem b, in the
+ * pattern's order; an entry index no problem's column range covers is left
+ * untouched.  Needs a factored handle (x, vp).  P_colptr == NULL: the pattern
+ * the handle got from dopt_conic_set_csc (out_nz of A_nnz entries) — sparse-route
+ * handles only, where it is kept; elsewhere −1. */
+int dopt_conic_reverse_grads_csc(dopt_handle* h, const double* g, const int64_t* P_colptr,
+                                 const int64_t* P_rowval, int64_t P_nnz, double* out_nz);
 /* Caps LSQR at `maxiter` iterations (0 restores the reference's default,
  * IterativeSolvers' maxiter = max(size(M)) = n + m + 1: ConicProgram.jl:323,
  * :372); a run that reaches the cap reports istop 7.  A parity instrument:
@@ -316,7 +399,8 @@ int dopt_conic_lsqr_norms(dopt_handle* h, double* norms);
  * sides ≤ 64, not dopt_set_sparse): groups of up to 4 seeds co-iterate in one
  * workgroup and share every sweep over A (k = 1: the single-seed kernel).
  * Split route and sparse route: the single-seed LSQR once per seed inside the
- * call — no shared sweep there yet.
+ * call — no shared sweep there yet.  The _k calls keep dense tangents and a
+ * dense out_dA (no `_csc` form).
  * After a _k call dopt_conic_lsqr_stats, dopt_conic_lsqr_norms, dopt_get_info
  * and dopt_get_system_size report seed 0. */
 int dopt_conic_reverse_k(dopt_handle* h, int32_t k, const double* dx, double* out_g,
