@@ -206,7 +206,7 @@ int dopt_destroy(dopt_handle* h) {
     (void)hipStreamDestroy(h->crit);
   }
   DevBuf* bufs[] = {&h->dinv, &h->plist, &h->lsqr_ws, &h->binv, &h->fwdw, &h->K, &h->ipiv, &h->s, &h->kidx, &h->meta, &h->rhs,
-                    &h->x, &h->cone_dev, &h->vp, &h->dpi, &h->cwork, &h->cinfo, &h->cnorm, &h->cinfok, &h->csplit, &h->krhs, &h->kx,
+                    &h->x, &h->cone_dev, &h->vp, &h->dpi, &h->cwork, &h->cinfo, &h->cnorm, &h->cinfok, &h->cjac, &h->csplit, &h->krhs, &h->kx,
                     &h->kfull, &h->kamax, &h->nlp_map, &h->nlp_shift, &h->nlp_scale, &h->kls, &h->gk, &h->glist,
                     &h->mws, &h->qsy, &h->psd_eig, &h->psd_app, &h->ukp, &h->nlp_rd, &h->nlp_ri, &h->nlp_t1, &h->nlp_t2,
                     &h->nlp_msc, &h->pack, &h->tpack, &h->rpack};
@@ -1868,6 +1868,60 @@ int dopt_conic_lsqr_stats_k(dopt_handle* h, int32_t k, int32_t* stats) {
     DOPT_CHECK_HIP(hipMemcpyAsync(stats, h->cinfok.p, (size_t)2 * h->batch * k * sizeof(int32_t),
                                   hipMemcpyDeviceToHost, h->stream));
     DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+// ---- conic parameter accumulation (params.hip) ----
+int dopt_conic_params_forward(dopt_handle* h, const double* dp, int32_t nparam, int64_t nterms,
+                              const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                              const double* t_coef, double* db, double* dc) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_params_forward on a non-conic handle");
+    if ((nparam > 0 && !dp) || (h->m && !db) || (h->n && !dc))
+      throw Error(-1, "dp, db (m > 0) and dc (n > 0) are required");
+    const size_t B = h->batch, n = h->n, m = h->m, P = nparam > 0 ? (size_t)nparam : 0;
+    const double* d = P ? stage_in(*h, h->tin[0], dp, B * P) : nullptr;
+    double* ob = m ? out_ptr(*h, h->tout[4], db, B * m) : nullptr;
+    double* oc = n ? out_ptr(*h, h->tout[5], dc, B * n) : nullptr;
+    dopt::conic_params_forward(*h, d, nparam, nterms, t_param, t_kind, t_index, t_coef, ob, oc);
+    if (m) copy_out(*h, db, ob, B * m);
+    if (n) copy_out(*h, dc, oc, B * n);
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int dopt_conic_params_reverse(dopt_handle* h, const double* g, int32_t nparam, int64_t nterms,
+                              const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                              const double* t_coef, double* out_dp) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_params_reverse on a non-conic handle");
+    if (!g || (nparam > 0 && !out_dp)) throw Error(-1, "g and out_dp are required");
+    const size_t B = h->batch, N = (size_t)h->n + h->m + 1, P = nparam > 0 ? (size_t)nparam : 0;
+    const double* gd = stage_in(*h, h->tin[0], g, B * N);
+    double* o = P ? out_ptr(*h, h->tout[0], out_dp, B * P) : nullptr;
+    dopt::conic_params_reverse(*h, gd, nparam, nterms, t_param, t_kind, t_index, t_coef, o);
+    if (P) copy_out(*h, out_dp, o, B * P);
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    return 0;
+  });
+}
+
+int dopt_conic_params_jacobian(dopt_handle* h, int32_t mode, int32_t nparam, int64_t nterms,
+                               const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                               const double* t_coef, double* out_J, int32_t* stats) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_params_jacobian on a non-conic handle");
+    h->conic_k = 0;   // the chunks' _k calls are not the caller's: `stats` is the way to read the runs
+    const size_t cnt = (size_t)h->batch * h->n * (nparam > 0 ? (size_t)nparam : 0);
+    if (cnt && !out_J) throw Error(-1, "out_J is required");
+    Timer tm;
+    double* o = cnt ? out_ptr(*h, h->tout[0], out_J, cnt) : nullptr;
+    dopt::conic_params_jacobian(*h, mode, nparam, nterms, t_param, t_kind, t_index, t_coef, o, stats);
+    if (cnt) copy_out(*h, out_J, o, cnt);
+    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    h->last_time = tm.s();
     return 0;
   });
 }

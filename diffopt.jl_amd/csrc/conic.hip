@@ -2921,6 +2921,12 @@ void conic_reverse_grads_at(Handle& h, const double* g, const CscArg& P, double*
   check_launch();
 }
 
+size_t conic_seed_doubles(const Handle& h) {
+  const size_t N = (size_t)h.n + h.m + 1;
+  return SeqVec::len(N, h.m, h.n) + N;   // conic_run's cwork: a sequence's vectors and its right-hand side
+}
+int conic_seed_group() { return LSQRK_G; }
+
 // seed j's block of a seed-major array of k·B·len doubles (null stays null)
 template <class T>
 static T* seed_block(T* p, int j, size_t len) { return p ? p + j * len : nullptr; }

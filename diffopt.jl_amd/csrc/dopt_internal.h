@@ -245,6 +245,7 @@ struct Handle {
   DevBuf vp, dpi, cwork, cinfo, cnorm;   // cnorm: LSQR terminal estimates, 8·B doubles
   DevBuf cinfok;                // multi-seed calls: per seed [istop | iterations], 2·B·k int32
   int32_t conic_k = 0;          // seeds of the last conic call if it was a _k call, else 0
+  DevBuf cjac;                  // dopt_conic_params_jacobian: a chunk's materialised seeds and LSQR solutions
   DevBuf csplit;                // split-path LSQR vectors, partial products, state
   int32_t conic_split = -1;     // -1 auto, 0 persistent kernel, 1 split (env DOPT_CONIC_SPLIT)
   int32_t lsqr_cap = 0;         // LSQR iteration cap (0: IterativeSolvers' maxiter = N; dopt_conic_set_maxiter)
@@ -516,6 +517,19 @@ void conic_forward_reverse_csc(Handle& h, const SpStore& dA, const int* err, con
 void conic_reverse_grads_at(Handle& h, const double* g, const CscArg& P, double* out_nz, int* err);
 void conic_forward_k(Handle& h, int k, const double* dA, const double* db, const double* dc, double* out,
                      double* out_dx);
+// what conic_run sizes per seed of a _k call and problem (cwork doubles), and the widest seed group that shares a
+// sweep over A (conic.hip); the parameter Jacobian sizes its chunks by them
+size_t conic_seed_doubles(const Handle& h);
+int conic_seed_group();
+// conic parameter accumulation (params.hip): dopt_conic_params_forward / _reverse / _jacobian on device pointers
+void conic_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
+                          const int32_t* t_kind, const int32_t* t_index, const double* t_coef, double* db,
+                          double* dc);
+void conic_params_reverse(Handle& h, const double* g, int nparam, int64_t nterms, const int32_t* t_param,
+                          const int32_t* t_kind, const int32_t* t_index, const double* t_coef, double* out);
+void conic_params_jacobian(Handle& h, int mode, int nparam, int64_t nterms, const int32_t* t_param,
+                           const int32_t* t_kind, const int32_t* t_index, const double* t_coef, double* out_J,
+                           int32_t* stats);
 
 inline int64_t round_up(int64_t a, int64_t b) { return (a + b - 1) / b * b; }
 

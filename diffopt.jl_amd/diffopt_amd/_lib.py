@@ -89,6 +89,12 @@ SIGNATURES = {
     "dopt_conic_reverse_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 5),
     "dopt_conic_forward_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 5),
     "dopt_conic_lsqr_stats_k": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_void_p]),
+    "dopt_conic_params_forward": (ctypes.c_int, [_h, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]
+                                  + [ctypes.c_void_p] * 6),
+    "dopt_conic_params_reverse": (ctypes.c_int, [_h, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]
+                                  + [ctypes.c_void_p] * 5),
+    "dopt_conic_params_jacobian": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_int32, ctypes.c_int64]
+                                   + [ctypes.c_void_p] * 6),
     "dopt_nlp_set_structure": (ctypes.c_int, [_h, ctypes.c_void_p, ctypes.c_void_p, ctypes.c_void_p,
                                               ctypes.c_int32]),
     "dopt_nlp_set": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 12),

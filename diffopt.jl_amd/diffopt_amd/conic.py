@@ -9,7 +9,9 @@ Mirrors ``DiffOpt.ConicProgram`` (reference ``src/ConicProgram/ConicProgram.jl``
   ``forward_differentiate`` (:257-334), ``reverse_differentiate`` (:336-394),
   ``ForwardVariablePrimal`` (:403-412), ``ReverseObjectiveFunction``
   (:396-401), ``ReverseConstraintFunction`` (``_get_dA``/``_get_db``
-  :414-443), and MAX-sense handling of ``c`` (:206-208).
+  :414-443), and MAX-sense handling of ``c`` (:206-208); with a term table,
+  ``ForwardConstraintSet`` / ``ReverseConstraintSet`` of parameters
+  (``src/parameters.jl``).
 """
 
 import ctypes
@@ -284,6 +286,82 @@ class ConicBatch:
         buf = buf.reshape(k, 2, B)
         return {"istop": buf[:, 0, :], "iterations": buf[:, 1, :]}
 
+    # ---- parameters (ParametricOptInterface glue, reference src/parameters.jl)
+    @staticmethod
+    def _terms(terms):
+        """terms: iterable of (param, kind, index, coef) — kinds 0 constraint row
+        (ProductOfSets order), 2 objective, 3 objective parameter×variable
+        (index = v); kind 1 is the QP's and is refused here."""
+        t = list(terms)
+        par = np.ascontiguousarray([int(x[0]) for x in t], dtype=np.int32)
+        kind = np.ascontiguousarray([int(x[1]) for x in t], dtype=np.int32)
+        idx = np.ascontiguousarray([int(x[2]) for x in t], dtype=np.int32)
+        coef = np.ascontiguousarray([float(x[3]) for x in t], dtype=np.float64)
+        return len(t), par, kind, idx, coef
+
+    def params_forward(self, dp, terms):
+        """Parameter tangents dp (B, nparam) → (db (B, m), dc (B, n)), ready for
+        ``forward(None, db, dc)`` — dopt_conic_params_forward.  db is NOT
+        negated (the conic ``_fill`` runs with ``S -> false``)."""
+        B, n, m = self.batch, self.n, self.m
+        nparam = int(dp.shape[1])
+        nt, par, kind, idx, coef = self._terms(terms)
+        st = self._stage([dp])
+        d = vector(dp, (B, nparam))
+        dev = st.mem == _lib.DOPT_MEM_DEVICE
+        db, dc = Staged.empty((B, m), dev), Staged.empty((B, n), dev)
+        p = Staged.ptr
+        rc = self.lib.dopt_conic_params_forward(self.h, st.ptr(d) if nparam else None, nparam, nt, p(par), p(kind),
+                                                p(idx), p(coef), st.ptr(db) if m else None,
+                                                st.ptr(dc) if n else None)
+        _lib.check(rc, self.h)
+        return db, dc
+
+    def params_reverse(self, g, terms, nparam):
+        """ReverseConstraintSet of every parameter of every problem, (B, nparam),
+        from a reverse call's ``g`` (B, N) — dopt_conic_params_reverse."""
+        B = self.batch
+        nparam = int(nparam)
+        nt, par, kind, idx, coef = self._terms(terms)
+        st = self._stage([g])
+        gv = vector(g, (B, self.N))
+        out = Staged.empty((B, nparam), st.mem == _lib.DOPT_MEM_DEVICE)
+        p = Staged.ptr
+        rc = self.lib.dopt_conic_params_reverse(self.h, st.ptr(gv), nparam, nt, p(par), p(kind), p(idx), p(coef),
+                                                st.ptr(out) if nparam else None)
+        _lib.check(rc, self.h)
+        return out
+
+    def params_jacobian(self, terms, nparam, mode, device=False):
+        """dx/dp of every problem by unit seeds (dopt_conic_params_jacobian) →
+        (J (B, n, nparam), stats).  ``mode`` 0 (or "forward"): column j is
+        ``forward(None, *params_forward(e_j))``'s dx; 1 (or "reverse"): row i is
+        ``params_reverse(reverse(e_i).g)``; each bit-identical to those calls.
+        The reference's two directions are not adjoint (its reverse solve runs
+        LSQR on M, not Mᵀ), so the two Jacobians differ and there is no mode
+        that chooses between them.  stats: dict of (K, B) arrays "istop" and
+        "iterations", K = nparam (mode 0) or n (mode 1), always numpy.  J is a
+        numpy array, or with ``device`` a torch CUDA tensor written in place by
+        the kernels (on torch's current stream)."""
+        mode = {"forward": 0, "reverse": 1}.get(mode, mode)
+        B, n = self.batch, self.n
+        nparam = int(nparam)
+        nt, par, kind, idx, coef = self._terms(terms)
+        K = n if mode == 1 else nparam
+        J = Staged.empty((K, B, nparam if mode == 1 else n), device)
+        self._stage([J] if device else [])   # the memory mode (and torch's stream) follow the output
+        buf = np.zeros(2 * B * max(K, 1), dtype=np.int32)
+        p = Staged.ptr
+        rc = self.lib.dopt_conic_params_jacobian(self.h, int(mode), nparam, nt, p(par), p(kind), p(idx), p(coef),
+                                                 p(J) if K and B and n else None, buf.ctypes.data)
+        _lib.check(rc, self.h)
+        buf = buf.reshape(max(K, 1), 2, B)[:K]
+        if device:
+            J = J.permute(1, 2, 0) if mode == 0 else J.permute(1, 0, 2)
+        else:
+            J = J.transpose(1, 2, 0) if mode == 0 else J.transpose(1, 0, 2)
+        return J, {"istop": buf[:, 0, :], "iterations": buf[:, 1, :]}
+
     def set_maxiter(self, maxiter):
         """Cap LSQR at ``maxiter`` iterations (0: the reference's default
         max(size(M))) — dopt_conic_set_maxiter."""
@@ -349,13 +427,23 @@ class Model:
         self.input_dx = {}
         self.input_objective = None
         self.input_constraints = {}   # cone index -> (coeffs (dim×n), constants (dim))
+        self.param_terms, self.nparam = [], 0
+        self.input_dp = {}            # parameter -> ForwardConstraintSet direction
+        self.back_param_cache = None
 
-    def set_problem(self, A, b, c, cones, max_sense=False):
+    def set_problem(self, A, b, c, cones, max_sense=False, param_terms=(), nparam=0):
+        """``param_terms``: the parametric terms (param, kind, index, coef) of
+        the problem's ``nparam`` parameters (``ConicBatch._terms``: kind 0 a
+        constraint row in ProductOfSets order, 2 the objective, 3 objective
+        parameter×variable)."""
         self.A = np.asarray(A, dtype=np.float64)
         self.b = np.asarray(b, dtype=np.float64)
         self.c = np.asarray(c, dtype=np.float64)
         self.cones = [(int(k), int(d)) for k, d in cones]
         self.max_sense = bool(max_sense)
+        self.param_terms = [tuple(t) for t in param_terms]
+        self.nparam = int(nparam)
+        self.input_dp = {}
         self._engine = None
 
     def rows(self, ci):
@@ -383,6 +471,12 @@ class Model:
     def set_forward_constraint_function(self, ci, coeffs, constants):
         self.input_constraints[int(ci)] = (np.asarray(coeffs, float), np.asarray(constants, float))
 
+    def set_forward_parameter(self, p, value):
+        """``ForwardConstraintSet`` of ``ParameterRef(p)``: the direction ``Parameter(value)``."""
+        if not 0 <= int(p) < self.nparam:
+            raise IndexError(f"parameter {p} of {self.nparam}")
+        self.input_dp[int(p)] = float(value)
+
     def _ensure(self):
         m = self.A.shape[0]
         if self.y is None or np.any(np.isnan(self.y)) or len(self.y) < m:
@@ -409,6 +503,12 @@ class Model:
             dA[r] = cf
             db[r] = k
         dc = np.zeros(n) if self.input_objective is None else self.input_objective
+        if self.input_dp:   # the parameters' tangents on top of the functions' (parameters.jl:120-145, :226-275)
+            dp = np.zeros((1, self.nparam))
+            for p, v in self.input_dp.items():
+                dp[0, p] = v
+            pb, pc = e.params_forward(dp, self.param_terms)
+            db, dc = db + np.asarray(pb)[0], dc + np.asarray(pc)[0]
         out, dx = e.forward(dA[None], db[None], dc[None])
         self.forw_grad_cache = (np.asarray(out)[0], np.asarray(dx)[0])
         self.diff_time = time.perf_counter() - t0
@@ -421,6 +521,8 @@ class Model:
             dx[i] = v
         g, dA, db, dc = e.reverse(dx[None])
         self.back_grad_cache = tuple(np.asarray(a)[0] for a in (g, dA, db, dc))
+        self.back_param_cache = (np.asarray(e.params_reverse(g, self.param_terms, self.nparam))[0]
+                                 if self.nparam else None)
         self.diff_time = time.perf_counter() - t0
 
     def forward_variable_primal(self, i):
@@ -434,6 +536,10 @@ class Model:
         r = self.rows(ci)
         _, dA, db, _ = self.back_grad_cache
         return dA[r], db[r]
+
+    def reverse_parameter(self, p):
+        """``ReverseConstraintSet`` of ``ParameterRef(p)`` (parameters.jl:365-388, :463-509)."""
+        return float(self.back_param_cache[p])
 
     def differentiate_time_sec(self):
         return self.diff_time

@@ -411,6 +411,59 @@ int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const doub
  * iterations (B)].  −1 if the last conic call was not a _k call with this k. */
 int dopt_conic_lsqr_stats_k(dopt_handle* h, int32_t k, int32_t* stats);
 
+/* ---- parameters of a cone program (reference src/parameters.jl:341-534
+ * consuming ConicProgram.jl:396-443; test/parameters.jl:103-152) -------------
+ * Terms as dopt_qp_params_*: (t_param, t_kind, t_index, t_coef), host memory in
+ * both memory modes, identical for every problem, sums in term order.  Kinds
+ * keep the QP numbers where they mean the same thing:
+ *   0  parameter term of constraint row t_index ∈ [0, m), ProductOfSets row
+ *      order (ParametricVectorAffineFunction; the caller maps output_index to
+ *      the row)
+ *   2  parameter term of the objective (t_index ignored)
+ *   3  parameter×variable term of the objective, variable t_index ∈ [0, n)
+ * kind 1 and anything else is refused (−1, "parameter accumulation: term T out
+ * of range").
+ * Forward (parameters.jl:120-145, :226-275, then ConicProgram.jl:270-287):
+ * from dp (nparam×B), dopt_conic_forward's inputs db (m×B) and dc (n×B),
+ * written in full: db_i = +Σ c·dp over row i's kind-0 terms — no negation:
+ * the conic `_fill` runs with S -> false, unlike the QP's dh / db —, dc_v =
+ * Σ c·dp over kind 3; kind 2 is dropped.
+ * Reverse (parameters.jl:365-388, :463-509): out_dp (nparam×B) = Σ_t c_t·s_t
+ * from a reverse call's out_g ((n+m+1)×B): s = the value dopt_conic_reverse
+ * writes to out_db[i], g[n+i] − g[n+m]·vp[i] (kind 0), to out_dc[v],
+ * g[v] − g[n+m]·x[v] (kind 3), 0 (kind 2: ReverseObjectiveFunction's constant
+ * is 0.0, ConicProgram.jl:400).  Needs x and vp: factorises first if needed.
+ * The two directions are NOT adjoint: reverse_differentiate! runs lsqr on M,
+ * not Mᵀ (ConicProgram.jl:372, TODO :381-384), and M is singular at every
+ * exact primal-dual point. */
+int dopt_conic_params_forward(dopt_handle* h, const double* dp, int32_t nparam, int64_t nterms,
+                              const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                              const double* t_coef, double* db, double* dc);
+int dopt_conic_params_reverse(dopt_handle* h, const double* g, int32_t nparam, int64_t nterms,
+                              const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                              const double* t_coef, double* out_dp);
+/* The parameter Jacobian by unit seeds; each direction restates its k
+ * reference calls (they are different objects, see above: there is no mode that
+ * picks one for the caller).  mode 0: out_J is n×B×nparam, seed-major as every
+ * _k output: block j = the out_dx of dopt_conic_forward(NULL, db_j, dc_j) with
+ * (db_j, dc_j) = dopt_conic_params_forward(e_j) (ForwardConstraintSet of
+ * parameter j = 1, forward_differentiate!, ForwardVariablePrimal).  mode 1:
+ * out_J is nparam×B×n: block i = dopt_conic_params_reverse of the out_g of
+ * dopt_conic_reverse(dx = e_i) (ReverseVariablePrimal of variable i = 1,
+ * reverse_differentiate!, ReverseConstraintSet of every parameter).  Any
+ * other mode: −1.  The seeds run through dopt_conic_forward_k / _reverse_k in
+ * chunks (sized from a workspace bound; env DOPT_CONIC_JAC_CHUNK=<k> overrides)
+ * and every block is bit-identical to those single calls on its seed, whatever
+ * the chunk.  A parameter whose terms never enter (none, or kind 2 only) has
+ * an exactly zero right-hand side: its mode-0 block is 0 with istop 0
+ * (ConicProgram.jl:320).  stats (host memory, may be NULL): 2·B·K int32, K =
+ * nparam (mode 0) or n (mode 1), laid out as dopt_conic_lsqr_stats_k.  nparam =
+ * 0 or n = 0 writes nothing and returns 0.  After the call
+ * dopt_conic_lsqr_stats_k returns −1. */
+int dopt_conic_params_jacobian(dopt_handle* h, int32_t mode, int32_t nparam, int64_t nterms,
+                               const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                               const double* t_coef, double* out_J, int32_t* stats);
+
 /* ---- introspection ---------------------------------------------------------*/
 /* per-problem status of the last factor/solve: QP: 0 ok, k>0 zero pivot at
  * column k of the reference's KKT matrix LHS (unknowns [z; λ; ν], 1-based;
