@@ -462,6 +462,7 @@ class MI355XSolver:
         self.device = device
         self._h = None
         self._key = None
+        self._single = True    # the last solve_system's LHS was one matrix, not a batch (resolve)
         self._fact = None      # (memory key of the array factorised last, the array)
         self.resolves = 0      # calls served by dopt_lhs_resolve (introspection)
         self.lib = _lib.load()
@@ -513,6 +514,7 @@ class MI355XSolver:
         rhs = np.ascontiguousarray(np.transpose(Rk, (2, 0, 1)))   # seed-major (k, B, rows)
         out = np.empty_like(rhs)
         h = self._handle(B, rows)
+        self._single = single
         # the reference's second call per model passes LHS' (an adjoint of the
         # LHS it just solved with: QuadraticProgram.jl:335, :438): an array
         # that is exactly the transpose of the one factorised last (same
@@ -542,6 +544,42 @@ class MI355XSolver:
         if vec:
             X = X[..., 0]
         return X[0] if single else X
+
+    def resolve(self, RHS, trans=False):
+        """A further solve on the factors of the last non-iterative
+        ``solve_system`` (dopt_lhs_resolve): ``LHS \\ RHS``, or ``LHS' \\ RHS``
+        with `trans`.  RHS shaped as that call's (batched exactly when its LHS
+        was); raises SingularException(info) again if that LHS was singular."""
+        if self._h is None:
+            raise _lib.EngineError(-1, "resolve: no solve_system call on this solver yet")
+        B, rows = self._key
+        R = np.asarray(RHS, dtype=np.float64)
+        single = self._single
+        if single:
+            R = R[None]
+        vec = R.ndim == 2
+        Rk = R[..., None] if vec else R
+        if Rk.ndim != 3 or Rk.shape[:2] != (B, rows):
+            raise TypeError("RHS does not match the factorised LHS")
+        k = Rk.shape[2]
+        rhs = np.ascontiguousarray(np.transpose(Rk, (2, 0, 1)))
+        out = np.empty_like(rhs)
+        rc = self.lib.dopt_lhs_resolve(self._h, k, rhs.ctypes.data, out.ctypes.data, int(bool(trans)))
+        self.resolves += 1
+        _lib.check(rc, self._h)
+        X = np.transpose(out, (1, 2, 0))
+        if vec:
+            X = X[..., 0]
+        return X[0] if single else X
+
+    def lu_kind(self):
+        """Per-problem factorisation kind of the last ``solve_system``:
+        _lib.LU_KIND_NOPIV / LU_KIND_PIVOT (dopt_qp_get_lu_kind)."""
+        if self._h is None:
+            raise _lib.EngineError(-1, "lu_kind: no solve_system call on this solver yet")
+        buf = np.zeros(self._key[0], dtype=np.int8)
+        _lib.check(self.lib.dopt_qp_get_lu_kind(self._h, buf.ctypes.data), self._h)
+        return buf
 
 
 def solve_system(LHS, RHS, iterative=False, device=0, solver=None):
