@@ -54,6 +54,14 @@ void copy_out(Handle& h, double* dst, const double* dev, size_t count) {
   DOPT_CHECK_HIP(hipMemcpyAsync(dst, dev, count * sizeof(double), hipMemcpyDeviceToHost, h.stream));
 }
 
+void wait(Handle& h) { DOPT_CHECK_HIP(hipStreamSynchronize(h.stream)); }
+
+// `bytes` of device memory copied into `dst` (host), waited for
+void read_back(Handle& h, void* dst, const void* src, size_t bytes) {
+  DOPT_CHECK_HIP(hipMemcpyAsync(dst, src, bytes, hipMemcpyDeviceToHost, h.stream));
+  wait(h);
+}
+
 // A singular problem's info in the coordinates of the reference's LHS
 // (QuadraticProgram.jl:256-282, unknowns [z; λ; ν]): the factorised system
 // is the reduced one (kept inequality rows only), so a reduced column k maps
@@ -63,19 +71,21 @@ int full_column(Handle& h, int64_t b, const dopt::QPMeta& mm) {
   if (k <= n) return k;
   if (k <= n + mm.nk) {
     int32_t row = 0;
-    DOPT_CHECK_HIP(hipMemcpyAsync(&row, h.kidx.as<int32_t>() + (size_t)b * h.m + (k - n - 1), sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, h.stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+    read_back(h, &row, h.kidx.as<int32_t>() + (size_t)b * h.m + (k - n - 1), sizeof(int32_t));
     return n + row + 1;
   }
   return n + h.m + (k - n - mm.nk);
 }
 
-int first_info(Handle& h) {
+// the factorisation's per-problem metadata, read back
+std::vector<dopt::QPMeta> read_meta(Handle& h) {
   std::vector<dopt::QPMeta> meta(h.batch);
-  DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h.meta.p, h.batch * sizeof(dopt::QPMeta),
-                                hipMemcpyDeviceToHost, h.stream));
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+  read_back(h, meta.data(), h.meta.p, h.batch * sizeof(dopt::QPMeta));
+  return meta;
+}
+
+int first_info(Handle& h) {
+  const std::vector<dopt::QPMeta> meta = read_meta(h);
   for (int64_t b = 0; b < h.batch; ++b)
     if (!meta[b].iterative && meta[b].info > 0) return full_column(h, b, meta[b]);
   return 0;
@@ -88,34 +98,69 @@ struct Timer {
   }
 };
 
-// One conic call through the staging buffers.  `in` / `out` list the arrays
-// that take part: the caller's pointer (host or device by the handle's
-// memory mode; null: absent), its slot in tin[] / tout[], and its doubles per
-// seed; k seeds scale every count.  `call` gets the device pointers in list
-// order; the outputs are copied back and the stream drained after it.
-struct ConicIn {
+// An on-pattern gradient's values through the staging buffers: host mode
+// copies the caller's array in first, so that the entries no problem's range
+// covers come back as they were
+double* nz_out_ptr(Handle& h, DevBuf& buf, double* dst, size_t count) {
+  if (!dst || h.mem == DOPT_MEM_DEVICE) return dst;
+  buf.ensure(std::max<size_t>(count, 1) * sizeof(double));
+  if (count) DOPT_CHECK_HIP(hipMemcpyAsync(buf.p, dst, count * sizeof(double), hipMemcpyHostToDevice, h.stream));
+  return buf.as<double>();
+}
+
+// One call through the staging buffers.  `in` / `out` list the arrays that
+// take part: the caller's pointer (host or device by the handle's memory
+// mode; null: absent), its slot in tin[] / tout[], and its doubles per seed;
+// k seeds scale every count.  `call` gets the device pointers in list order;
+// the copies in are queued before it and the copies out after it.  How the
+// call ends (a wait, first_info, csc_err_wait, a stream-ordered return) is the
+// entry's own.
+struct In {
   const double* p;
   int slot;
   size_t count;
 };
-struct ConicOut {
+struct Out {
   double* p;
   int slot;
   size_t count;
+  bool keep = false;   // an on-pattern gradient: the caller's values go in first (nz_out_ptr)
 };
+template <class T, int N>
+struct Args {
+  T v[N];
+  int n = 0;
+  Args() = default;
+  Args(std::initializer_list<T> l) {
+    for (const T& a : l) v[n++] = a;
+  }
+};
+using Ins = Args<In, 7>;
+using Outs = Args<Out, 6>;
 template <class F>
-void conic_call(Handle& h, size_t k, std::initializer_list<ConicIn> in, std::initializer_list<ConicOut> out,
-                F&& call) {
-  const double* ip[4];
+void staged_call(Handle& h, size_t k, const Ins& in, const Outs& out, F&& call) {
+  const double* ip[7];
   double* op[6];
-  int i = 0;
-  for (const ConicIn& a : in) ip[i++] = stage_in(h, h.tin[a.slot], a.p, k * a.count);
-  i = 0;
-  for (const ConicOut& a : out) op[i++] = out_ptr(h, h.tout[a.slot], a.p, k * a.count);
+  for (int i = 0; i < in.n; ++i) ip[i] = stage_in(h, h.tin[in.v[i].slot], in.v[i].p, k * in.v[i].count);
+  for (int i = 0; i < out.n; ++i) {
+    const Out& a = out.v[i];
+    op[i] = (a.keep ? nz_out_ptr : out_ptr)(h, h.tout[a.slot], a.p, k * a.count);
+  }
   call(ip, op);
-  i = 0;
-  for (const ConicOut& a : out) copy_out(h, a.p, op[i++], k * a.count);
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+  for (int i = 0; i < out.n; ++i) copy_out(h, out.v[i].p, op[i], k * out.v[i].count);
+}
+
+// The seed (slot 0; null: none) and the six tangents (slots 1-6) of a QP call
+Ins qp_ins(const Handle& h, const double* dl_dz, const double* dQ, const double* dq, const double* dG,
+           const double* dh, const double* dA, const double* db) {
+  const size_t B = h.batch, n = h.n, m = h.m, p = h.p;
+  return {{dl_dz, 0, B * n}, {dQ, 1, B * n * n}, {dq, 2, B * n}, {dG, 3, B * m * n},
+          {dh, 4, B * m},    {dA, 5, B * p * n}, {db, 6, B * p}};
+}
+// ... and the tangents as the kernels take them, from six device pointers:
+// G's and A's are absent when the model has no such rows
+dopt::FwdTangents fwd_tangents(const Handle& h, const double* const* t) {
+  return {t[0], t[1], h.m ? t[2] : nullptr, h.m ? t[3] : nullptr, h.p ? t[4] : nullptr, h.p ? t[5] : nullptr};
 }
 
 }  // namespace
@@ -205,45 +250,27 @@ int dopt_destroy(dopt_handle* h) {
     (void)hipStreamSynchronize(h->crit);
     (void)hipStreamDestroy(h->crit);
   }
-  DevBuf* bufs[] = {&h->dinv, &h->plist, &h->lsqr_ws, &h->binv, &h->fwdw, &h->K, &h->ipiv, &h->s, &h->kidx, &h->meta, &h->rhs,
-                    &h->x, &h->cone_dev, &h->vp, &h->dpi, &h->cwork, &h->cinfo, &h->cnorm, &h->cinfok, &h->cjac, &h->csplit, &h->krhs, &h->kx,
-                    &h->kfull, &h->kamax, &h->nlp_map, &h->nlp_shift, &h->nlp_scale, &h->kls, &h->gk, &h->glist,
-                    &h->mws, &h->qsy, &h->psd_eig, &h->psd_app, &h->ukp, &h->nlp_rd, &h->nlp_ri, &h->nlp_t1, &h->nlp_t2,
-                    &h->nlp_msc, &h->pack, &h->tpack, &h->rpack};
-  for (auto* b : bufs) b->release();
-  for (auto& b : h->own_nin) b.release();
-  for (auto& b : h->own_in) b.release();
-  for (auto& b : h->csc_in) b.release();
-  for (auto& b : h->csc_in_val) b.release();
-  h->csc_err.release();
-  for (auto& st : h->spt)
-    for (DevBuf* b : {&st.cp, &st.ri, &st.rp, &st.ci, &st.rv}) b->release();
-  for (auto& b : h->spt_in) b.release();
-  for (auto& b : h->spt_val) b.release();
-  for (auto& b : h->own_cin) b.release();
-  for (auto& b : h->tin) b.release();
-  for (auto& b : h->tout) b.release();
   for (auto& pe : h->ev_pending) {
     (void)hipEventDestroy(pe.second.first);
     (void)hipEventDestroy(pe.second.second);
   }
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->meta_host) (void)hipHostFree(h->meta_host);
-  if (h->pin) (void)hipHostFree(h->pin);
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
-  if (h->pin_out) (void)hipHostFree(h->pin_out);
   if (h->meta_ev) (void)hipEventDestroy(h->meta_ev);
   if (h->meta_fork) (void)hipEventDestroy(h->meta_fork);
   if (h->own_stream && h->stream) (void)hipStreamDestroy(h->stream);
-  delete h;
+  delete h;   // every DevBuf and PinBuf frees itself
   return 0;
 }
+
+int64_t dopt_live_device_bytes(void) { return dopt::live_device_bytes.load(); }
 
 const char* dopt_last_error(const dopt_handle* h) { return h ? h->err.c_str() : "null handle"; }
 
 int dopt_set_stream(dopt_handle* h, void* stream) {
   return guarded(h, [&]() {
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     if (h->own_stream && h->stream) DOPT_CHECK_HIP(hipStreamDestroy(h->stream));
     h->own_stream = false;
     h->stream = static_cast<hipStream_t>(stream);  // NULL = legacy default stream
@@ -298,7 +325,7 @@ int dopt_qp_set(dopt_handle* h, const double* Q, const double* G, const double* 
     h->nu = p ? stage_in(*h, h->own_in[6], nu, B * p) : nullptr;
     h->set = true;
     h->factored = false;
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     return 0;
   });
 }
@@ -333,15 +360,9 @@ static bool pack_in(Handle& h, const PackIn* in, int k, const void** out, DevBuf
   size_t tot = 0;
   for (int i = 0; i < k; ++i) tot += (in[i].bytes + 15) & ~(size_t)15;
   if (tot == 0 || tot > PACK_MAX) return false;
-  if (h.pin_bytes < tot) {
-    if (h.pin) DOPT_CHECK_HIP(hipHostFree(h.pin));
-    h.pin = nullptr;
-    h.pin_bytes = 0;
-    DOPT_CHECK_HIP(hipHostMalloc(&h.pin, tot, hipHostMallocDefault));
-    h.pin_bytes = tot;
-  }
   // the previous call's copy out of the pinned buffer is complete: every
   // host-mode entry point synchronises before it returns
+  char* pin = h.pin.grow(tot);
   D.ensure(tot);
   size_t off = 0;
   for (int i = 0; i < k; ++i) {
@@ -349,11 +370,11 @@ static bool pack_in(Handle& h, const PackIn* in, int k, const void** out, DevBuf
       out[i] = nullptr;
       continue;
     }
-    std::memcpy(static_cast<char*>(h.pin) + off, in[i].src, in[i].bytes);
+    std::memcpy(pin + off, in[i].src, in[i].bytes);
     out[i] = static_cast<const char*>(D.p) + off;
     off += (in[i].bytes + 15) & ~(size_t)15;
   }
-  DOPT_CHECK_HIP(hipMemcpyAsync(D.p, h.pin, off, hipMemcpyHostToDevice, h.stream));
+  DOPT_CHECK_HIP(hipMemcpyAsync(D.p, pin, off, hipMemcpyHostToDevice, h.stream));
   return true;
 }
 
@@ -379,27 +400,110 @@ static int host_csc_check(const int64_t* cp, const int64_t* rv, int64_t nnz, siz
   return err;
 }
 
-// Pinned staging pays from a handle's third small call on (its hipHostMalloc
-// costs more than the pageable copies of a call or two save: a handle per
-// model — LHS then LHS' — stays pageable).
-static bool pin_ok(Handle& h) { return h.mem != DOPT_MEM_DEVICE && (h.pin_out || ++h.io_calls >= 3); }
+// Pinned or pageable, asked once per small-path or plug-point call: pinned
+// staging pays from a handle's third such call on, or as soon as the pinned
+// read-back buffer exists (its hipHostMalloc costs more than the pageable
+// copies of a call or two save: a handle per model — LHS then LHS' — stays
+// pageable).  Device mode stages nothing.
+static bool use_pinned(Handle& h) { return h.mem != DOPT_MEM_DEVICE && (h.pin_out.p || ++h.io_calls >= 3); }
 
-// The small path's pinned read-back buffer (the previous call's use of it is
-// complete: every entry point that uses it synchronises before it returns).
-// The small-path kernels read and write it in place, at pin_out_dev.
-static char* pin_out(Handle& h, size_t bytes) {
-  if (h.pin_out_bytes < bytes) {
-    if (h.pin_out) DOPT_CHECK_HIP(hipHostFree(h.pin_out));
-    h.pin_out = nullptr;
-    h.pin_out_dev = nullptr;
-    h.pin_out_bytes = 0;
-    DOPT_CHECK_HIP(hipHostMalloc(&h.pin_out, bytes, hipHostMallocDefault));
-    void* dp = nullptr;
-    DOPT_CHECK_HIP(hipHostGetDevicePointer(&dp, h.pin_out, 0));
-    h.pin_out_dev = static_cast<char*>(dp);
-    h.pin_out_bytes = bytes;
+// The transport of one small-path call (qp_small.hip): `nin` inputs (the seed
+// or the tangents; null: absent), `ob` bytes of outputs and `fb` bytes of
+// per-problem flags (0: the call has none).  The constructor yields the device
+// pointers to launch with, finish() waits and yields the host's view.
+//   pinned, in place   host mode, use_pinned, no matrix input: the kernel reads
+//                      the inputs from and writes [outputs | flags] to pin_out
+//   pinned, packed     ... a matrix input: the inputs by one copy (pack_in into
+//                      tpack), [outputs | flags] written to pin_out
+//   pageable           host mode otherwise (a handle's first calls, or inputs
+//                      the pack refuses): tin[slot + i] / tout[slot], one copy
+//                      each way
+//   borrowed           device mode: the caller's arrays; the flags in csc_err
+// (the previous call's use of pin_out is complete: every entry point that
+// uses it waits before it returns)
+struct SmallIO {
+  Handle& h;
+  const size_t ob, fb;
+  const bool host;
+  bool pinned;
+  const double* in[6] = {};
+  double* out = nullptr;
+  int32_t* flags = nullptr;
+  std::vector<char> page;
+  const char* view = nullptr;   // after finish(): [outputs | flags] on the host (device mode: the flags alone)
+
+  SmallIO(Handle& hh, const PackIn* src, int nin, bool matrix_in, int slot, double* dst, size_t obytes, size_t fbytes)
+      : h(hh), ob(obytes), fb(fbytes), host(hh.mem != DOPT_MEM_DEVICE), pinned(use_pinned(hh)) {
+    const void* pd[6];
+    if (pinned && matrix_in) pinned = pack_in(h, src, nin, pd, &h.tpack);
+    char* dev = nullptr;
+    if (pinned && matrix_in) {
+      for (int i = 0; i < nin; ++i) in[i] = static_cast<const double*>(pd[i]);
+      h.pin_out.grow(ob + fb);
+      dev = h.pin_out.dev;
+    } else if (pinned) {
+      size_t off[6], tot = (ob + fb + 15) & ~(size_t)15;
+      for (int i = 0; i < nin; ++i) off[i] = tot, tot += (src[i].bytes + 15) & ~(size_t)15;
+      char* pz = h.pin_out.grow(tot);
+      dev = h.pin_out.dev;
+      for (int i = 0; i < nin; ++i) {
+        if (!src[i].src) continue;
+        std::memcpy(pz + off[i], src[i].src, src[i].bytes);
+        in[i] = reinterpret_cast<const double*>(dev + off[i]);
+      }
+    } else if (host) {
+      for (int i = 0; i < nin; ++i)
+        in[i] = stage_in(h, h.tin[slot + i], static_cast<const double*>(src[i].src), src[i].bytes / sizeof(double));
+      h.tout[slot].ensure(ob + fb);
+      dev = h.tout[slot].as<char>();
+    } else {
+      for (int i = 0; i < nin; ++i) in[i] = static_cast<const double*>(src[i].src);
+      out = dst;
+      h.csc_err.ensure(fb);
+      flags = fb ? h.csc_err.as<int32_t>() : nullptr;
+      return;
+    }
+    out = reinterpret_cast<double*>(dev);
+    flags = fb ? reinterpret_cast<int32_t*>(dev + ob) : nullptr;
   }
-  return static_cast<char*>(h.pin_out);
+  // waits for the launch; true: no problem raised a flag
+  bool finish() {
+    if (pinned) {
+      view = h.pin_out.p;
+      wait(h);
+    } else {
+      page.resize(host ? ob + fb : fb);
+      if (!page.empty())
+        DOPT_CHECK_HIP(hipMemcpyAsync(page.data(), host ? static_cast<const void*>(out) : flags, page.size(),
+                                      hipMemcpyDeviceToHost, h.stream));
+      wait(h);
+      view = page.data();
+    }
+    const int32_t* hf = reinterpret_cast<const int32_t*>(view + (host ? ob : 0));
+    return std::all_of(hf, hf + fb / sizeof(int32_t), [](int32_t f) { return f == 0; });
+  }
+  void deliver(double* dst) const {
+    if (host) std::memcpy(dst, view, ob);
+  }
+};
+
+// The solution of a packed plug-point call (dopt_lhs_solve / _resolve): one
+// copy into the pinned read-back buffer, then the caller's array
+static void pinned_copy_out(Handle& h, double* dst, const double* dev, size_t count) {
+  char* pin = h.pin_out.grow(count * sizeof(double));
+  read_back(h, pin, dev, count * sizeof(double));
+  std::memcpy(dst, pin, count * sizeof(double));
+}
+
+// the message of a CSC setter's error word (bit 1: colptr, bit 2: rowval)
+static const char* csc_err_text(int err) {
+  return (err & 1) ? "CSC colptr is not monotone / out of range" : "CSC rowval out of range";
+}
+// ... the device's word (csc_err), read back
+static int csc_err_read(Handle& h) {
+  int herr = 0;
+  read_back(h, &herr, h.csc_err.p, sizeof(int));
+  return herr;
 }
 
 int dopt_qp_set_csc(dopt_handle* h,
@@ -433,53 +537,50 @@ int dopt_qp_set_csc(dopt_handle* h,
     } sync_on_throw{h->stream};
     h->csc_err.ensure(sizeof(int));
     int* err = h->csc_err.as<int>();
-    if (h->sparse) {   // kept sparse (sparse.hip): G, A and their CSR copies; Q only tested for zero
-      DOPT_CHECK_HIP(hipMemsetAsync(h->csc_err.p, 0, sizeof(int), h->stream));
-      const int64_t* cp[3];
-      const int64_t* rv[3];
-      const double* nz[3];
-      const int64_t nnz[3] = {Q_nnz, G_nnz, A_nnz};
-      const int64_t* icp[3] = {Q_colptr, G_colptr, A_colptr};
-      const int64_t* irv[3] = {Q_rowval, G_rowval, A_rowval};
-      const double* inz[3] = {Q_nzval, G_nzval, A_nzval};
-      const size_t rows[3] = {n, m, p};
-      for (int k = 0; k < 3; ++k) {
-        const bool on = rows[k] > 0;
-        cp[k] = on ? stage_in_i64(*h, h->csc_in[3 * k], icp[k], B * (n + 1)) : nullptr;
-        rv[k] = on && nnz[k] ? stage_in_i64(*h, h->csc_in[3 * k + 1], irv[k], (size_t)nnz[k]) : nullptr;
-        nz[k] = on && nnz[k] ? stage_in(*h, h->csc_in_val[k], inz[k], (size_t)nnz[k]) : nullptr;
-      }
-      dopt::sp_set_csc(*h, cp[0], rv[0], nz[0], nnz[0], cp[1], rv[1], nz[1], nnz[1], cp[2], rv[2], nz[2], nnz[2],
-                       err);
-      int herr = 0;
-      DOPT_CHECK_HIP(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      if (herr & 3) throw Error(-1, (herr & 1) ? "CSC colptr is not monotone / out of range"
-                                               : "CSC rowval out of range");
-      h->sp_qnz = (herr & 4) != 0;
-      h->Q = h->G = h->A = nullptr;
+    // Q, G, A: absent (no rows) matrices have no arrays, empty ones only a colptr
+    struct Mat { const int64_t *cp, *rv; const double* nz; int64_t nnz; size_t rows; int slot; };
+    Mat mats[3] = {{Q_colptr, Q_rowval, Q_nzval, Q_nnz, n, 0},
+                   {G_colptr, G_rowval, G_nzval, G_nnz, m, 1},
+                   {A_colptr, A_rowval, A_nzval, A_nnz, p, 3}};
+    for (Mat& M : mats) {
+      if (!M.rows) M.cp = nullptr;
+      if (!M.rows || !M.nnz) M.rv = nullptr, M.nz = nullptr;
+    }
+    // one matrix's arrays, each by its own copy (device mode: borrowed)
+    auto stage_mat = [&](int k) {
+      const Mat& M = mats[k];
+      return dopt::CscArg{stage_in_i64(*h, h->csc_in[3 * k], M.cp, B * (n + 1)),
+                          stage_in_i64(*h, h->csc_in[3 * k + 1], M.rv, (size_t)M.nnz),
+                          stage_in(*h, h->csc_in_val[k], M.nz, (size_t)M.nnz), M.nnz};
+    };
+    auto stage_vectors = [&]() {
       h->hv = m ? stage_in(*h, h->own_in[2], hv, B * m) : nullptr;
       h->z = stage_in(*h, h->own_in[4], z, B * n);
       h->lam = m ? stage_in(*h, h->own_in[5], lam, B * m) : nullptr;
       h->nu = p ? stage_in(*h, h->own_in[6], nu, B * p) : nullptr;
+    };
+    if (h->sparse) {   // kept sparse (sparse.hip): G, A and their CSR copies; Q only tested for zero
+      DOPT_CHECK_HIP(hipMemsetAsync(h->csc_err.p, 0, sizeof(int), h->stream));
+      const dopt::CscArg Q = stage_mat(0), G = stage_mat(1), A = stage_mat(2);
+      dopt::sp_set_csc(*h, Q.cp, Q.rv, Q.nz, Q.nnz, G.cp, G.rv, G.nz, G.nnz, A.cp, A.rv, A.nz, A.nnz, err);
+      const int herr = csc_err_read(*h);
+      if (herr & 3) throw Error(-1, csc_err_text(herr));
+      h->sp_qnz = (herr & 4) != 0;
+      h->Q = h->G = h->A = nullptr;
+      stage_vectors();
       h->set = true;
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      wait(*h);
       return 0;
     }
-    struct Mat { const int64_t *cp, *rv; const double* nz; int64_t nnz; size_t rows; int slot; };
-    const Mat mats[3] = {{Q_colptr, Q_rowval, Q_nzval, Q_nnz, n, 0},
-                         {G_colptr, G_rowval, G_nzval, G_nnz, m, 1},
-                         {A_colptr, A_rowval, A_nzval, A_nnz, p, 3}};
-    const double* dense[3] = {nullptr, nullptr, nullptr};
     // small models (the Julia back-end's batch of one): every array in one copy
     PackIn pin[13];
     const void* pdev[13];
     for (int k = 0; k < 3; ++k) {
       const Mat& M = mats[k];
       const bool on = M.rows > 0;
-      pin[3 * k] = {on ? M.cp : nullptr, on ? B * (n + 1) * sizeof(int64_t) : 0};
-      pin[3 * k + 1] = {on && M.nnz ? M.rv : nullptr, on ? (size_t)M.nnz * sizeof(int64_t) : 0};
-      pin[3 * k + 2] = {on && M.nnz ? M.nz : nullptr, on ? (size_t)M.nnz * sizeof(double) : 0};
+      pin[3 * k] = {M.cp, on ? B * (n + 1) * sizeof(int64_t) : 0};
+      pin[3 * k + 1] = {M.rv, on ? (size_t)M.nnz * sizeof(int64_t) : 0};
+      pin[3 * k + 2] = {M.nz, on ? (size_t)M.nnz * sizeof(double) : 0};
     }
     pin[9] = {m ? hv : nullptr, m ? B * m * sizeof(double) : 0};
     pin[10] = {z, B * n * sizeof(double)};
@@ -492,49 +593,35 @@ int dopt_qp_set_csc(dopt_handle* h,
     for (const PackIn& q : pin) pbytes += q.bytes;
     if (h->mem != DOPT_MEM_DEVICE && pbytes <= PACK_MAX / 2) {
       hostv = 0;
-      for (int k = 0; k < 3; ++k)
-        if (mats[k].rows > 0) hostv |= host_csc_check(mats[k].cp, mats[k].rv, mats[k].nnz, mats[k].rows, n, B);
-      if (hostv) throw Error(-1, (hostv & 1) ? "CSC colptr is not monotone / out of range" : "CSC rowval out of range");
+      for (const Mat& M : mats)
+        if (M.rows > 0) hostv |= host_csc_check(M.cp, M.rv, M.nnz, M.rows, n, B);
+      if (hostv) throw Error(-1, csc_err_text(hostv));
     }
     const bool packed = pack_in(*h, pin, 13, pdev);
     const bool async = packed && hostv == 0;
-    if (async) {   // validated on the host: Q, G and A zero-filled and scattered by ONE launch
-      dopt::CscTriple T{};
-      for (int k = 0; k < 3; ++k) {
-        const Mat& M = mats[k];
-        if (M.rows == 0) continue;
-        DevBuf& d = h->own_in[M.slot];
-        d.ensure(B * M.rows * n * sizeof(double));
-        T.cp[k] = (const int64_t*)pdev[3 * k];
-        T.rv[k] = (const int64_t*)pdev[3 * k + 1];
-        T.nz[k] = (const double*)pdev[3 * k + 2];
-        T.dense[k] = d.as<double>();
-        T.rows[k] = (int)M.rows;
-        dense[k] = d.as<double>();
-      }
-      dopt::csc_to_dense3(*h, T);
-    } else {
-      DOPT_CHECK_HIP(hipMemsetAsync(h->csc_err.p, 0, sizeof(int), h->stream));
-    }
-    for (int k = 0; k < 3 && !async; ++k) {
+    if (!async) DOPT_CHECK_HIP(hipMemsetAsync(h->csc_err.p, 0, sizeof(int), h->stream));
+    const double* dense[3] = {nullptr, nullptr, nullptr};
+    dopt::CscTriple T{};
+    for (int k = 0; k < 3; ++k) {
       const Mat& M = mats[k];
       if (M.rows == 0) continue;
-      const int64_t* cp = packed ? (const int64_t*)pdev[3 * k] : stage_in_i64(*h, h->csc_in[3 * k], M.cp, B * (n + 1));
-      const int64_t* rv = packed ? (const int64_t*)pdev[3 * k + 1]
-                                 : stage_in_i64(*h, h->csc_in[3 * k + 1], M.rv, (size_t)M.nnz);
-      const double* nz = packed ? (const double*)pdev[3 * k + 2] : stage_in(*h, h->csc_in_val[k], M.nz, (size_t)M.nnz);
+      const dopt::CscArg a = packed ? dopt::CscArg{(const int64_t*)pdev[3 * k], (const int64_t*)pdev[3 * k + 1],
+                                                   (const double*)pdev[3 * k + 2], M.nnz}
+                                    : stage_mat(k);
       DevBuf& d = h->own_in[M.slot];
       d.ensure(B * M.rows * n * sizeof(double));
-      dopt::csc_to_dense(*h, cp, rv ? rv : cp, nz ? nz : (const double*)d.p, M.nnz, (int)M.rows, (int)n,
-                         d.as<double>(), err);
       dense[k] = d.as<double>();
+      if (async) {   // validated on the host: Q, G and A zero-filled and scattered by ONE launch (below)
+        T.cp[k] = a.cp, T.rv[k] = a.rv, T.nz[k] = a.nz, T.dense[k] = d.as<double>(), T.rows[k] = (int)M.rows;
+      } else {
+        dopt::csc_to_dense(*h, a.cp, a.rv ? a.rv : a.cp, a.nz ? a.nz : (const double*)d.p, M.nnz, (int)M.rows,
+                           (int)n, d.as<double>(), err);
+      }
     }
-    if (!async) {
-      int herr = 0;
-      DOPT_CHECK_HIP(hipMemcpyAsync(&herr, err, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      if (herr) throw Error(-1, (herr & 1) ? "CSC colptr is not monotone / out of range"
-                                           : "CSC rowval out of range");
+    if (async) {
+      dopt::csc_to_dense3(*h, T);
+    } else if (const int herr = csc_err_read(*h)) {
+      throw Error(-1, csc_err_text(herr));
     }
     h->Q = dense[0];
     h->G = m ? dense[1] : nullptr;
@@ -545,10 +632,7 @@ int dopt_qp_set_csc(dopt_handle* h,
       h->lam = (const double*)pdev[11];
       h->nu = (const double*)pdev[12];
     } else {
-      h->hv = m ? stage_in(*h, h->own_in[2], hv, B * m) : nullptr;
-      h->z = stage_in(*h, h->own_in[4], z, B * n);
-      h->lam = m ? stage_in(*h, h->own_in[5], lam, B * m) : nullptr;
-      h->nu = p ? stage_in(*h, h->own_in[6], nu, B * p) : nullptr;
+      stage_vectors();
     }
     h->set = true;
     h->factored = false;
@@ -558,7 +642,7 @@ int dopt_qp_set_csc(dopt_handle* h,
       h->pin_pending = true;
       return 0;
     }
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     return 0;
   });
 }
@@ -581,15 +665,11 @@ int dopt_qp_reverse_grads(dopt_handle* h, const double* rev, double* dQ, double*
     if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_reverse_grads on a non-QP handle");
     if (!rev) throw Error(-1, "rev is required");
     const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
-    const double* r = stage_in(*h, h->tin[0], rev, B * L);
-    double* outs[6] = {dQ, dq, dG, g_const, dA, a_const};
-    const size_t cnt[6] = {B * n * n, B * n, B * m * n, B * m, B * p * n, B * p};
-    double* dev[6];
-    for (int k = 0; k < 6; ++k) dev[k] = outs[k] ? out_ptr(*h, h->tout[k], outs[k], cnt[k]) : nullptr;
-    dopt::qp_reverse_grads(*h, r, dev[0], dev[1], dev[2], dev[3], dev[4], dev[5]);
-    for (int k = 0; k < 6; ++k)
-      if (outs[k]) copy_out(*h, outs[k], dev[k], cnt[k]);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{rev, 0, B * L}},
+                {{dQ, 0, B * n * n}, {dq, 1, B * n}, {dG, 2, B * m * n}, {g_const, 3, B * m}, {dA, 4, B * p * n},
+                 {a_const, 5, B * p}},
+                [&](const double** i, double** o) { dopt::qp_reverse_grads(*h, i[0], o[0], o[1], o[2], o[3], o[4], o[5]); });
+    wait(*h);
     return 0;
   });
 }
@@ -601,11 +681,10 @@ int dopt_qp_params_reverse(dopt_handle* h, const double* rev, int32_t nparam, in
     if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_params_reverse on a non-QP handle");
     if (!rev || (nparam > 0 && !out_dp)) throw Error(-1, "rev and out_dp are required");
     const size_t B = h->batch, L = (size_t)h->n + h->m + h->p, P = nparam > 0 ? (size_t)nparam : 0;
-    const double* r = stage_in(*h, h->tin[0], rev, B * L);
-    double* o = P ? out_ptr(*h, h->tout[0], out_dp, B * P) : nullptr;
-    dopt::qp_params_reverse(*h, r, nparam, nterms, t_param, t_kind, t_index, t_coef, o);
-    if (P) copy_out(*h, out_dp, o, B * P);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{rev, 0, B * L}}, {{P ? out_dp : nullptr, 0, B * P}}, [&](const double** i, double** o) {
+      dopt::qp_params_reverse(*h, i[0], nparam, nterms, t_param, t_kind, t_index, t_coef, o[0]);
+    });
+    wait(*h);
     return 0;
   });
 }
@@ -618,15 +697,12 @@ int dopt_qp_params_forward(dopt_handle* h, const double* dp, int32_t nparam, int
     if ((nparam > 0 && !dp) || !dq || (h->m && !dh) || (h->p && !db))
       throw Error(-1, "dp, dq, dh (m > 0) and db (p > 0) are required");
     const size_t B = h->batch, n = h->n, m = h->m, p = h->p, P = nparam > 0 ? (size_t)nparam : 0;
-    const double* d = P ? stage_in(*h, h->tin[0], dp, B * P) : nullptr;
-    double* oq = out_ptr(*h, h->tout[0], dq, B * n);
-    double* oh = m ? out_ptr(*h, h->tout[1], dh, B * m) : nullptr;
-    double* ob = p ? out_ptr(*h, h->tout[2], db, B * p) : nullptr;
-    dopt::qp_params_forward(*h, d, nparam, nterms, t_param, t_kind, t_index, t_coef, oq, oh, ob);
-    copy_out(*h, dq, oq, B * n);
-    if (m) copy_out(*h, dh, oh, B * m);
-    if (p) copy_out(*h, db, ob, B * p);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{P ? dp : nullptr, 0, B * P}},
+                {{dq, 0, B * n}, {m ? dh : nullptr, 1, B * m}, {p ? db : nullptr, 2, B * p}},
+                [&](const double** i, double** o) {
+                  dopt::qp_params_forward(*h, i[0], nparam, nterms, t_param, t_kind, t_index, t_coef, o[0], o[1], o[2]);
+                });
+    wait(*h);
     return 0;
   });
 }
@@ -637,90 +713,32 @@ int dopt_qp_reverse(dopt_handle* h, const double* dl_dz, double* out) {
     if (!dl_dz || !out) throw Error(-1, "dl_dz and out are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, L = h->n + h->m + h->p;
-    const bool host = h->mem != DOPT_MEM_DEVICE;
-    const double* d = nullptr;
     if (h->sparse) {   // sparse route: LSQR on the implicit LHS (no singular verdict)
-      d = stage_in(*h, h->tin[0], dl_dz, B * n);
-      double* o = out_ptr(*h, h->tout[0], out, B * L);
-      dopt::sp_reverse(*h, d, o);
-      copy_out(*h, out, o, B * L);
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      staged_call(*h, 1, {{dl_dz, 0, B * n}}, {{out, 0, B * L}},
+                  [&](const double** i, double** o) { dopt::sp_reverse(*h, i[0], o[0]); });
+      wait(*h);
       h->last_time = tm.s();
       return 0;
     }
     // a model not yet factorised, batch of a few: the one-launch small path
-    // (qp_small.hip); in host mode from a handle's third call on no copy at
-    // all — the kernel reads the seed from and writes the outputs and the
-    // per-problem flags to the pinned read-back buffer (the first calls: one
-    // copy each way); anything it cannot take runs the batched route below
+    // (qp_small.hip) through SmallIO's transport — in host mode from a handle's
+    // third call on no copy at all; anything it cannot take (a problem's flag
+    // set) runs the batched route below
+    const double* staged = nullptr;
     if (!h->factored && dopt::qp_small_eligible(*h)) {
-      const size_t ob = B * L * sizeof(double), fb = B * sizeof(int32_t);
-      const bool pinned = pin_ok(*h);
-#ifndef DOPT_SMALL_COPY   // (A/B: DOPT_SMALL_COPY builds the copy-in / copy-out form of round 5)
-      if (host && pinned) {
-        const size_t so = (ob + fb + 15) & ~(size_t)15;
-        char* pz = pin_out(*h, so + B * n * sizeof(double));
-        std::memcpy(pz + so, dl_dz, B * n * sizeof(double));
-        const int32_t* hf = reinterpret_cast<const int32_t*>(pz + ob);
-        char* pd = h->pin_out_dev;
-        dopt::qp_small_reverse(*h, reinterpret_cast<const double*>(pd + so), reinterpret_cast<double*>(pd),
-                               reinterpret_cast<int32_t*>(pd + ob));
-        DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-        h->small_ready = std::all_of(hf, hf + B, [](int32_t f) { return f == 0; });
-        if (h->small_ready) {
-          std::memcpy(out, pz, ob);
-          h->last_time = tm.s();
-          return 0;
-        }
+      const PackIn seed[1] = {{dl_dz, B * n * sizeof(double)}};
+      SmallIO io(*h, seed, 1, false, 0, out, B * L * sizeof(double), B * sizeof(int32_t));
+      dopt::qp_small_reverse(*h, io.in[0], io.out, io.flags);
+      h->small_ready = io.finish();
+      if (h->small_ready) {
+        io.deliver(out);
+        h->last_time = tm.s();
+        return 0;
       }
-#else
-      if (host && pinned) {
-        const PackIn pi[1] = {{dl_dz, B * n * sizeof(double)}};
-        const void* pd[1];
-        if (pack_in(*h, pi, 1, pd, &h->tpack)) {
-          h->tout[0].ensure(ob + fb);
-          dopt::qp_small_reverse(*h, static_cast<const double*>(pd[0]), h->tout[0].as<double>(),
-                                 reinterpret_cast<int32_t*>(h->tout[0].as<char>() + ob));
-          char* pz = pin_out(*h, ob + fb);
-          DOPT_CHECK_HIP(hipMemcpyAsync(pz, h->tout[0].p, ob + fb, hipMemcpyDeviceToHost, h->stream));
-          DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-          const int32_t* hf = reinterpret_cast<const int32_t*>(pz + ob);
-          h->small_ready = std::all_of(hf, hf + B, [](int32_t f) { return f == 0; });
-          if (h->small_ready) {
-            std::memcpy(out, pz, ob);
-            h->last_time = tm.s();
-            return 0;
-          }
-        }
-      }
-#endif
-      if (!(host && pinned)) {   // a handle's first calls (pageable), device mode
-        if (host) {
-          d = stage_in(*h, h->tin[0], dl_dz, B * n);
-          h->tout[0].ensure(ob + fb);
-        } else {
-          d = dl_dz;
-          h->csc_err.ensure(fb);
-        }
-        double* o = host ? h->tout[0].as<double>() : out;
-        int32_t* flags = host ? reinterpret_cast<int32_t*>(h->tout[0].as<char>() + ob) : h->csc_err.as<int32_t>();
-        dopt::qp_small_reverse(*h, d, o, flags);
-        std::vector<char> page(host ? ob + fb : fb);
-        DOPT_CHECK_HIP(hipMemcpyAsync(page.data(), host ? static_cast<const void*>(o) : static_cast<const void*>(flags),
-                                      page.size(), hipMemcpyDeviceToHost, h->stream));
-        DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-        const int32_t* hf = reinterpret_cast<const int32_t*>(page.data() + (host ? ob : 0));
-        h->small_ready = std::all_of(hf, hf + B, [](int32_t f) { return f == 0; });
-        if (h->small_ready) {
-          if (host) std::memcpy(out, page.data(), ob);
-          h->last_time = tm.s();
-          return 0;
-        }
-      }
+      if (!io.pinned) staged = io.in[0];   // the seed is in tin[0] already (device mode: the caller's)
     }
-    if (!d) d = stage_in(*h, h->tin[0], dl_dz, B * n);
     double* o = out_ptr(*h, h->tout[0], out, B * L);
-    dopt::qp_reverse(*h, d, o);
+    dopt::qp_reverse(*h, staged ? staged : stage_in(*h, h->tin[0], dl_dz, B * n), o);
     copy_out(*h, out, o, B * L);
     const int rc = first_info(*h);
     h->last_time = tm.s();
@@ -735,87 +753,28 @@ int dopt_qp_forward(dopt_handle* h, const double* dQ, const double* dq, const do
     if (!out) throw Error(-1, "out is required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
-#ifndef DOPT_SMALL_COPY
-    // the small path's factors with only vector tangents (dq, dh, db; the
-    // matrix ones zero): no copy at all — the kernel reads them from and
-    // writes its outputs into the pinned read-back buffer
-    if (!h->sparse && !h->factored && h->small_ready && pin_ok(*h) && !dQ && !(m && dG) && !(p && dA)) {
-      const size_t ob = B * L * sizeof(double), so = (ob + 15) & ~(size_t)15;
-      const size_t vq = B * n * sizeof(double), vh = B * m * sizeof(double), vb = B * p * sizeof(double);
-      const size_t oq = so, oh = oq + ((vq + 15) & ~(size_t)15), obb = oh + ((vh + 15) & ~(size_t)15);
-      char* pz = pin_out(*h, obb + vb + 16);
-      if (dq) std::memcpy(pz + oq, dq, vq);
-      if (m && dh) std::memcpy(pz + oh, dh, vh);
-      if (p && db) std::memcpy(pz + obb, db, vb);
-      char* pd = h->pin_out_dev;
-      dopt::qp_small_forward(*h, dopt::FwdTangents{nullptr, dq ? reinterpret_cast<const double*>(pd + oq) : nullptr,
-                                                   nullptr, m && dh ? reinterpret_cast<const double*>(pd + oh) : nullptr,
-                                                   nullptr, p && db ? reinterpret_cast<const double*>(pd + obb) : nullptr},
-                             reinterpret_cast<double*>(pd));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      std::memcpy(out, pz, ob);
+    // the small path's factors (dopt_qp_reverse).  Vector tangents only (dq,
+    // dh, db; the matrix ones zero): SmallIO's in-place form, no copy at all;
+    // a matrix tangent: one packed copy in
+    if (!h->sparse && !h->factored && h->small_ready) {
+      const PackIn tan[6] = {{dQ, B * n * n * sizeof(double)}, {dq, B * n * sizeof(double)},
+                             {m ? dG : nullptr, B * m * n * sizeof(double)}, {m ? dh : nullptr, B * m * sizeof(double)},
+                             {p ? dA : nullptr, B * p * n * sizeof(double)}, {p ? db : nullptr, B * p * sizeof(double)}};
+      SmallIO io(*h, tan, 6, tan[0].src || tan[2].src || tan[4].src, 1, out, B * L * sizeof(double), 0);
+      dopt::qp_small_forward(*h, fwd_tangents(*h, io.in), io.out);
+      io.finish();
+      io.deliver(out);
       h->last_time = tm.s();
       return 0;
     }
-#endif
-    if (!h->sparse && !h->factored && h->small_ready && pin_ok(*h)) {   // the small path's factors (dopt_qp_reverse): one copy in
-      const PackIn pi[6] = {{dQ, B * n * n * sizeof(double)}, {dq, B * n * sizeof(double)},
-                            {m ? dG : nullptr, B * m * n * sizeof(double)}, {m ? dh : nullptr, B * m * sizeof(double)},
-                            {p ? dA : nullptr, B * p * n * sizeof(double)}, {p ? db : nullptr, B * p * sizeof(double)}};
-      const void* pd[6];
-      if (pack_in(*h, pi, 6, pd, &h->tpack)) {
-        // the outputs straight into the pinned read-back buffer (no copy)
-        const size_t ob = B * L * sizeof(double);
-        char* pin = pin_out(*h, ob);
-#ifdef DOPT_SMALL_COPY
-        h->tout[1].ensure(ob);
-        dopt::qp_small_forward(*h, dopt::FwdTangents{static_cast<const double*>(pd[0]), static_cast<const double*>(pd[1]),
-                                                     static_cast<const double*>(pd[2]), static_cast<const double*>(pd[3]),
-                                                     static_cast<const double*>(pd[4]), static_cast<const double*>(pd[5])},
-                               h->tout[1].as<double>());
-        DOPT_CHECK_HIP(hipMemcpyAsync(pin, h->tout[1].p, ob, hipMemcpyDeviceToHost, h->stream));
-        DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(out, pin, ob);
-        h->last_time = tm.s();
-        return 0;
-#endif
-        dopt::qp_small_forward(*h, dopt::FwdTangents{static_cast<const double*>(pd[0]), static_cast<const double*>(pd[1]),
-                                                     static_cast<const double*>(pd[2]), static_cast<const double*>(pd[3]),
-                                                     static_cast<const double*>(pd[4]), static_cast<const double*>(pd[5])},
-                               reinterpret_cast<double*>(h->pin_out_dev));
-        DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-        std::memcpy(out, pin, ob);
-        h->last_time = tm.s();
-        return 0;
-      }
-    }
-    const double* a = stage_in(*h, h->tin[1], dQ, B * n * n);
-    const double* b = stage_in(*h, h->tin[2], dq, B * n);
-    const double* c = stage_in(*h, h->tin[3], dG, B * m * n);
-    const double* d = stage_in(*h, h->tin[4], dh, B * m);
-    const double* e = stage_in(*h, h->tin[5], dA, B * p * n);
-    const double* f = stage_in(*h, h->tin[6], db, B * p);
-    double* o = out_ptr(*h, h->tout[1], out, B * L);
-    if (h->sparse) {
-      dopt::sp_forward(*h, dopt::FwdTangents{a, b, m ? c : nullptr, m ? d : nullptr, p ? e : nullptr, p ? f : nullptr},
-                       o);
-      copy_out(*h, out, o, B * L);
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      h->last_time = tm.s();
-      return 0;
-    }
-    if (!h->factored && h->small_ready) {   // the small path's factors (dopt_qp_reverse)
-      dopt::qp_small_forward(*h, dopt::FwdTangents{a, b, m ? c : nullptr, m ? d : nullptr, p ? e : nullptr,
-                                                   p ? f : nullptr},
-                             o);
-      copy_out(*h, out, o, B * L);
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      h->last_time = tm.s();
-      return 0;
-    }
-    dopt::qp_forward(*h, a, b, c, d, e, f, o);
-    copy_out(*h, out, o, B * L);
-    const int rc = first_info(*h);
+    int rc = 0;
+    staged_call(*h, 1, qp_ins(*h, nullptr, dQ, dq, dG, dh, dA, db), {{out, 1, B * L}},
+                [&](const double** i, double** o) {
+                  if (h->sparse) dopt::sp_forward(*h, fwd_tangents(*h, i + 1), o[0]);
+                  else dopt::qp_forward(*h, i[1], i[2], i[3], i[4], i[5], i[6], o[0]);
+                });
+    if (h->sparse) wait(*h);
+    else rc = first_info(*h);
     h->last_time = tm.s();
     return rc;
   });
@@ -828,11 +787,9 @@ int dopt_qp_reverse_k(dopt_handle* h, int32_t k, const double* dl_dz, double* ou
     if (!dl_dz || !out) throw Error(-1, "dl_dz and out are required");
     if (k <= 0) throw Error(-1, "k must be positive");
     Timer tm;
-    const size_t B = h->batch, n = h->n, L = h->n + h->m + h->p, K = (size_t)k;
-    const double* d = stage_in(*h, h->tin[0], dl_dz, K * B * n);
-    double* o = out_ptr(*h, h->tout[0], out, K * B * L);
-    dopt::qp_reverse_k(*h, k, d, o);
-    copy_out(*h, out, o, K * B * L);
+    const size_t B = h->batch, n = h->n, L = h->n + h->m + h->p;
+    staged_call(*h, k, {{dl_dz, 0, B * n}}, {{out, 0, B * L}},
+                [&](const double** i, double** o) { dopt::qp_reverse_k(*h, k, i[0], o[0]); });
     const int rc = first_info(*h);
     h->last_time = tm.s();
     return rc;
@@ -847,16 +804,11 @@ int dopt_qp_forward_k(dopt_handle* h, int32_t k, const double* dQ, const double*
     if (!out) throw Error(-1, "out is required");
     if (k <= 0) throw Error(-1, "k must be positive");
     Timer tm;
-    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p, K = (size_t)k;
-    const double* a = stage_in(*h, h->tin[1], dQ, K * B * n * n);
-    const double* b = stage_in(*h, h->tin[2], dq, K * B * n);
-    const double* c = stage_in(*h, h->tin[3], dG, K * B * m * n);
-    const double* d = stage_in(*h, h->tin[4], dh, K * B * m);
-    const double* e = stage_in(*h, h->tin[5], dA, K * B * p * n);
-    const double* f = stage_in(*h, h->tin[6], db, K * B * p);
-    double* o = out_ptr(*h, h->tout[1], out, K * B * L);
-    dopt::qp_forward_k(*h, k, a, b, c, d, e, f, o);
-    copy_out(*h, out, o, K * B * L);
+    const size_t L = (size_t)h->n + h->m + h->p;
+    staged_call(*h, k, qp_ins(*h, nullptr, dQ, dq, dG, dh, dA, db), {{out, 1, h->batch * L}},
+                [&](const double** i, double** o) {
+                  dopt::qp_forward_k(*h, k, i[1], i[2], i[3], i[4], i[5], i[6], o[0]);
+                });
     const int rc = first_info(*h);
     h->last_time = tm.s();
     return rc;
@@ -871,36 +823,28 @@ int dopt_qp_forward_reverse(dopt_handle* h, const double* dl_dz, const double* d
     if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_forward_reverse on a non-QP handle");
     if (!dl_dz || !out_rev || !out_fwd) throw Error(-1, "dl_dz, out_rev and out_fwd are required");
     Timer tm;
-    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
-    const double* r = stage_in(*h, h->tin[0], dl_dz, B * n);
-    const double* a = stage_in(*h, h->tin[1], dQ, B * n * n);
-    const double* b = stage_in(*h, h->tin[2], dq, B * n);
-    const double* c = stage_in(*h, h->tin[3], dG, B * m * n);
-    const double* d = stage_in(*h, h->tin[4], dh, B * m);
-    const double* e = stage_in(*h, h->tin[5], dA, B * p * n);
-    const double* f = stage_in(*h, h->tin[6], db, B * p);
-    double* o1 = out_ptr(*h, h->tout[0], out_rev, B * L);
-    double* o2 = out_ptr(*h, h->tout[1], out_fwd, B * L);
-    if (h->sparse) {   // both LSQR runs in one launch; device mode returns stream-ordered
-      h->factored = false;
-      dopt::sp_forward_reverse(*h, r, dopt::FwdTangents{a, b, m ? c : nullptr, m ? d : nullptr, p ? e : nullptr,
-                                                        p ? f : nullptr},
-                               o1, o2);
-      copy_out(*h, out_rev, o1, B * L);
-      copy_out(*h, out_fwd, o2, B * L);
-      if (h->mem != DOPT_MEM_DEVICE) DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      h->last_time = tm.s();
-      return 0;
+    const size_t B = h->batch, L = (size_t)h->n + h->m + h->p;
+    const bool device = h->mem == DOPT_MEM_DEVICE;
+    staged_call(*h, 1, qp_ins(*h, dl_dz, dQ, dq, dG, dh, dA, db), {{out_rev, 0, B * L}, {out_fwd, 1, B * L}},
+                [&](const double** i, double** o) {
+                  h->factored = false;  // one solve = factor + fwd + rev (the factors are kept for later calls)
+                  if (h->sparse) {      // both LSQR runs in one launch
+                    dopt::sp_forward_reverse(*h, i[0], fwd_tangents(*h, i + 1), o[0], o[1]);
+                  } else {
+                    h->info_clear = false;
+                    dopt::qp_forward_reverse(*h, i[0], i[1], i[2], i[3], i[4], i[5], i[6], o[0], o[1]);
+                  }
+                });
+    // device mode returns stream-ordered (the outputs land on the handle's
+    // stream, i.e. the caller's): the sparse route always, the dense one with
+    // every info known to be 0; else the synchronous check of the first
+    // singular problem (the sparse route has no such verdict: a plain wait)
+    int rc = 0;
+    if (h->sparse) {
+      if (!device) wait(*h);
+    } else if (!(device && h->info_clear)) {
+      rc = first_info(*h);
     }
-    h->factored = false;  // one solve = factor + fwd + rev (the factors are kept for later calls)
-    h->info_clear = false;
-    dopt::qp_forward_reverse(*h, r, a, b, c, d, e, f, o1, o2);
-    copy_out(*h, out_rev, o1, B * L);
-    copy_out(*h, out_fwd, o2, B * L);
-    // device mode with every info known to be 0: stream-ordered return (the
-    // outputs land on the handle's stream, i.e. the caller's); else the
-    // synchronous check of the first singular problem
-    const int rc = (h->mem == DOPT_MEM_DEVICE && h->info_clear) ? 0 : first_info(*h);
     h->last_time = tm.s();
     return rc;
   });
@@ -967,13 +911,10 @@ int dopt_qp_forward_csc(dopt_handle* h,
     const dopt::CscArg T[3] = {stage_csc(*h, 0, dQ_colptr, dQ_rowval, dQ_nzval, dQ_nnz, true),
                                stage_csc(*h, 1, m ? dG_colptr : nullptr, dG_rowval, dG_nzval, dG_nnz, true),
                                stage_csc(*h, 2, p ? dA_colptr : nullptr, dA_rowval, dA_nzval, dA_nnz, true)};
-    const double* b = stage_in(*h, h->tin[2], dq, B * n);
-    const double* d = stage_in(*h, h->tin[4], m ? dh : nullptr, B * m);
-    const double* f = stage_in(*h, h->tin[6], p ? db : nullptr, B * p);
-    double* o = out_ptr(*h, h->tout[1], out, B * L);
-    int* err = csc_err_clear(*h);
-    dopt::sp_forward_csc(*h, T, b, d, f, o, err);
-    copy_out(*h, out, o, B * L);
+    staged_call(*h, 1, {{dq, 2, B * n}, {m ? dh : nullptr, 4, B * m}, {p ? db : nullptr, 6, B * p}}, {{out, 1, B * L}},
+                [&](const double** i, double** o) {
+                  dopt::sp_forward_csc(*h, T, i[0], i[1], i[2], o[0], csc_err_clear(*h));
+                });
     csc_err_wait(*h);
     h->last_time = tm.s();
     return 0;
@@ -995,31 +936,16 @@ int dopt_qp_forward_reverse_csc(dopt_handle* h, const double* dl_dz,
     const dopt::CscArg T[3] = {stage_csc(*h, 0, dQ_colptr, dQ_rowval, dQ_nzval, dQ_nnz, true),
                                stage_csc(*h, 1, m ? dG_colptr : nullptr, dG_rowval, dG_nzval, dG_nnz, true),
                                stage_csc(*h, 2, p ? dA_colptr : nullptr, dA_rowval, dA_nzval, dA_nnz, true)};
-    const double* r = stage_in(*h, h->tin[0], dl_dz, B * n);
-    const double* b = stage_in(*h, h->tin[2], dq, B * n);
-    const double* d = stage_in(*h, h->tin[4], m ? dh : nullptr, B * m);
-    const double* f = stage_in(*h, h->tin[6], p ? db : nullptr, B * p);
-    double* o1 = out_ptr(*h, h->tout[0], out_rev, B * L);
-    double* o2 = out_ptr(*h, h->tout[1], out_fwd, B * L);
-    int* err = csc_err_clear(*h);
-    h->factored = false;   // as dopt_qp_forward_reverse: one solve = factor + fwd + rev
-    dopt::sp_forward_reverse_csc(*h, r, T, b, d, f, o1, o2, err);
-    copy_out(*h, out_rev, o1, B * L);
-    copy_out(*h, out_fwd, o2, B * L);
+    staged_call(*h, 1, {{dl_dz, 0, B * n}, {dq, 2, B * n}, {m ? dh : nullptr, 4, B * m}, {p ? db : nullptr, 6, B * p}},
+                {{out_rev, 0, B * L}, {out_fwd, 1, B * L}}, [&](const double** i, double** o) {
+                  int* err = csc_err_clear(*h);
+                  h->factored = false;   // as dopt_qp_forward_reverse: one solve = factor + fwd + rev
+                  dopt::sp_forward_reverse_csc(*h, i[0], T, i[1], i[2], i[3], o[0], o[1], err);
+                });
     csc_err_wait(*h);
     h->last_time = tm.s();
     return 0;
   });
-}
-
-// An on-pattern gradient's values through the staging buffers: host mode
-// copies the caller's array in first, so that the entries no problem's range
-// covers come back as they were
-static double* nz_out_ptr(Handle& h, DevBuf& buf, double* dst, size_t count) {
-  if (!dst || h.mem == DOPT_MEM_DEVICE) return dst;
-  buf.ensure(std::max<size_t>(count, 1) * sizeof(double));
-  if (count) DOPT_CHECK_HIP(hipMemcpyAsync(buf.p, dst, count * sizeof(double), hipMemcpyHostToDevice, h.stream));
-  return buf.as<double>();
 }
 
 int dopt_qp_reverse_grads_csc(dopt_handle* h, const double* rev,
@@ -1036,16 +962,11 @@ int dopt_qp_reverse_grads_csc(dopt_handle* h, const double* rev,
     const dopt::CscArg P[3] = {stage_csc(*h, 0, outs[0] ? Q_colptr : nullptr, Q_rowval, nullptr, Q_nnz, false),
                                stage_csc(*h, 1, outs[1] ? G_colptr : nullptr, G_rowval, nullptr, G_nnz, false),
                                stage_csc(*h, 2, outs[2] ? A_colptr : nullptr, A_rowval, nullptr, A_nnz, false)};
-    const double* r = stage_in(*h, h->tin[0], rev, B * L);
     size_t cnt[3];
-    double* dev[3];
-    for (int k = 0; k < 3; ++k) {
-      cnt[k] = !outs[k] ? 0 : P[k].cp ? (size_t)P[k].nnz : (size_t)h->sp[k - 1].nnz;
-      dev[k] = nz_out_ptr(*h, h->tout[k], outs[k], cnt[k]);
-    }
-    int* err = csc_err_clear(*h);
-    dopt::sp_reverse_grads_at(*h, r, P, dev, err);
-    for (int k = 0; k < 3; ++k) copy_out(*h, outs[k], dev[k], cnt[k]);
+    for (int k = 0; k < 3; ++k) cnt[k] = !outs[k] ? 0 : P[k].cp ? (size_t)P[k].nnz : (size_t)h->sp[k - 1].nnz;
+    staged_call(*h, 1, {{rev, 0, B * L}},
+                {{outs[0], 0, cnt[0], true}, {outs[1], 1, cnt[1], true}, {outs[2], 2, cnt[2], true}},
+                [&](const double** i, double** o) { dopt::sp_reverse_grads_at(*h, i[0], P, o, csc_err_clear(*h)); });
     csc_err_wait(*h);
     return 0;
   });
@@ -1103,7 +1024,7 @@ int dopt_nlp_set_structure(dopt_handle* h, const int32_t* con_kind, const int8_t
     h->nlp_map.ensure(map.size() * sizeof(int32_t));
     DOPT_CHECK_HIP(hipMemcpyAsync(h->nlp_map.p, map.data(), map.size() * sizeof(int32_t), hipMemcpyHostToDevice,
                                   h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     h->nstruct = true;
     h->nset = false;
     h->nlp_spec_off = false;   // a new structure: the speculative LU launch is tried again
@@ -1132,7 +1053,7 @@ int dopt_nlp_set(dopt_handle* h, const double* Hxx, const double* Hxp, const dou
     for (int k = 0; k < 12; ++k) h->nin[k] = cnt[k] ? stage_in(*h, h->own_nin[k], src[k], cnt[k]) : nullptr;
     h->nset = true;
     h->nfactored = false;
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     return 0;
   });
 }
@@ -1164,7 +1085,7 @@ static void set_kkt(Handle& h, int32_t rows, int32_t num_w, int32_t num_cons, co
 int dopt_nlp_set_kkt(dopt_handle* h, int32_t rows, int32_t num_w, int32_t num_cons, const double* M) {
   return guarded(h, [&]() {
     set_kkt(*h, rows, num_w, num_cons, M, nullptr);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     return 0;
   });
 }
@@ -1199,13 +1120,9 @@ int dopt_nlp_forward(dopt_handle* h, const double* dp, double* dx, double* ddual
     Timer tm;
     const size_t B = h->batch, nd = (size_t)h->m + h->nlp_nlowp + h->nlp_nupp;
     static const double zero = 0.0;
-    const double* d = h->p ? stage_in(*h, h->tin[0], dp, B * h->p) : &zero;
-    double* ox = out_ptr(*h, h->tout[0], dx, B * h->n);
-    double* od = out_ptr(*h, h->tout[1], ddual, B * nd);
-    dopt::nlp_forward(*h, d, ox, od);
-    copy_out(*h, dx, ox, B * h->n);
-    copy_out(*h, ddual, od, B * nd);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{h->p ? dp : nullptr, 0, B * h->p}}, {{dx, 0, B * h->n}, {ddual, 1, B * nd}},
+                [&](const double** i, double** o) { dopt::nlp_forward(*h, h->p ? i[0] : &zero, o[0], o[1]); });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1217,12 +1134,9 @@ int dopt_nlp_reverse(dopt_handle* h, const double* dx, const double* ddual, doub
     if (h->p && !dp) throw Error(-1, "dp is required");
     Timer tm;
     const size_t B = h->batch, nd = (size_t)h->m + h->nlp_nlowp + h->nlp_nupp;
-    const double* ix = stage_in(*h, h->tin[0], dx, B * h->n);
-    const double* id = stage_in(*h, h->tin[1], ddual, B * nd);
-    double* op = out_ptr(*h, h->tout[0], dp, B * h->p);
-    dopt::nlp_reverse(*h, ix, id, op);
-    copy_out(*h, dp, op, B * h->p);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{dx, 0, B * h->n}, {ddual, 1, B * nd}}, {{dp, 0, B * h->p}},
+                [&](const double** i, double** o) { dopt::nlp_reverse(*h, i[0], i[1], o[0]); });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1237,17 +1151,12 @@ int dopt_nlp_forward_reverse(dopt_handle* h, const double* dp, const double* dx_
     Timer tm;
     const size_t B = h->batch, nd = (size_t)h->m + h->nlp_nlowp + h->nlp_nupp;
     static const double zero = 0.0;
-    const double* d = h->p ? stage_in(*h, h->tin[0], dp, B * h->p) : &zero;
-    const double* ix = stage_in(*h, h->tin[1], dx_seed, B * h->n);
-    const double* id = stage_in(*h, h->tin[2], ddual_seed, B * nd);
-    double* ox = out_ptr(*h, h->tout[0], dx_out, B * h->n);
-    double* od = out_ptr(*h, h->tout[1], ddual_out, B * nd);
-    double* op = out_ptr(*h, h->tout[2], dp_out, B * h->p);
-    dopt::nlp_forward_reverse(*h, d, ix, id, ox, od, op);
-    copy_out(*h, dx_out, ox, B * h->n);
-    copy_out(*h, ddual_out, od, B * nd);
-    copy_out(*h, dp_out, op, B * h->p);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{h->p ? dp : nullptr, 0, B * h->p}, {dx_seed, 1, B * h->n}, {ddual_seed, 2, B * nd}},
+                {{dx_out, 0, B * h->n}, {ddual_out, 1, B * nd}, {dp_out, 2, B * h->p}},
+                [&](const double** i, double** o) {
+                  dopt::nlp_forward_reverse(*h, h->p ? i[0] : &zero, i[1], i[2], o[0], o[1], o[2]);
+                });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1258,10 +1167,8 @@ int dopt_nlp_jacobian(dopt_handle* h, double* ds) {
     if (h->kind != DOPT_KIND_NLP) throw Error(-1, "dopt_nlp_jacobian on a non-NLP handle");
     if (!ds) throw Error(-1, "ds is required");
     const size_t cnt = (size_t)h->batch * h->nlp_rows * h->p;
-    double* o = out_ptr(*h, h->tout[0], ds, cnt);
-    dopt::nlp_jacobian(*h, o);
-    copy_out(*h, ds, o, cnt);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {}, {{ds, 0, cnt}}, [&](const double**, double** o) { dopt::nlp_jacobian(*h, o[0]); });
+    wait(*h);
     return 0;
   });
 }
@@ -1272,11 +1179,9 @@ int dopt_nlp_kkt_solve(dopt_handle* h, int32_t k, const double* rhs, double* x) 
     if (k <= 0) throw Error(-1, "k must be positive");
     if (!rhs || !x) throw Error(-1, "rhs and x are required");
     const size_t cnt = (size_t)k * h->batch * h->nlp_rows;
-    const double* r = stage_in(*h, h->tin[0], rhs, cnt);
-    double* o = out_ptr(*h, h->tout[0], x, cnt);
-    dopt::nlp_kkt_solve(*h, k, r, o);
-    copy_out(*h, x, o, cnt);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{rhs, 0, cnt}}, {{x, 0, cnt}},
+                [&](const double** i, double** o) { dopt::nlp_kkt_solve(*h, k, i[0], o[0]); });
+    wait(*h);
     return 0;
   });
 }
@@ -1294,21 +1199,19 @@ int dopt_lhs_solve(dopt_handle* h, int32_t rows, const double* M, int32_t k, con
     const PackIn pi[2] = {{M, mcnt * sizeof(double)}, {rhs, cnt * sizeof(double)}};
     const void* pd[2] = {nullptr, nullptr};
     const bool small = (mcnt + cnt) * sizeof(double) <= LHS_PACK_MAX && M && rhs && x && cnt &&
-                       h->kind == DOPT_KIND_NLP && pin_ok(*h) && pack_in(*h, pi, 2, pd, &h->tpack);
+                       h->kind == DOPT_KIND_NLP && use_pinned(*h) && pack_in(*h, pi, 2, pd, &h->tpack);
     set_kkt(*h, rows, rows, 0, M, small ? static_cast<const double*>(pd[0]) : nullptr);
     if (k <= 0) throw Error(-1, "k must be positive");
     if (!rhs || !x) throw Error(-1, "rhs and x are required");
-    const double* r = small ? static_cast<const double*>(pd[1]) : stage_in(*h, h->tin[0], rhs, cnt);
-    double* o = out_ptr(*h, h->tout[0], x, cnt);
-    dopt::lhs_solve(*h, k, r, o, iterative != 0, info.data());
     if (small) {
-      char* pin = pin_out(*h, cnt * sizeof(double));
-      DOPT_CHECK_HIP(hipMemcpyAsync(pin, o, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      std::memcpy(x, pin, cnt * sizeof(double));
+      double* o = out_ptr(*h, h->tout[0], x, cnt);
+      dopt::lhs_solve(*h, k, static_cast<const double*>(pd[1]), o, iterative != 0, info.data());
+      pinned_copy_out(*h, x, o, cnt);
     } else {
-      copy_out(*h, x, o, cnt);
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      staged_call(*h, 1, {{rhs, 0, cnt}}, {{x, 0, cnt}}, [&](const double** i, double** o) {
+        dopt::lhs_solve(*h, k, i[0], o[0], iterative != 0, info.data());
+      });
+      wait(*h);
     }
     h->last_time = tm.s();
     return 0;
@@ -1331,18 +1234,16 @@ int dopt_lhs_resolve(dopt_handle* h, int32_t k, const double* rhs, double* x, in
     const void* pd[1] = {nullptr};
     // (its own device buffer: tpack still holds M when dopt_lhs_solve packed it,
     // and nin[0] points there for a later re-factorisation)
-    const bool small = cnt * sizeof(double) <= LHS_PACK_MAX && pin_ok(*h) && pack_in(*h, pi, 1, pd, &h->rpack);
-    const double* r = small ? static_cast<const double*>(pd[0]) : stage_in(*h, h->tin[0], rhs, cnt);
-    double* o = out_ptr(*h, h->tout[0], x, cnt);
-    dopt::lhs_resolve(*h, k, r, o, trans != 0, info.data());
+    const bool small = cnt * sizeof(double) <= LHS_PACK_MAX && use_pinned(*h) && pack_in(*h, pi, 1, pd, &h->rpack);
     if (small) {   // (as dopt_lhs_solve: one pinned copy each way)
-      char* pin = pin_out(*h, cnt * sizeof(double));
-      DOPT_CHECK_HIP(hipMemcpyAsync(pin, o, cnt * sizeof(double), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-      std::memcpy(x, pin, cnt * sizeof(double));
+      double* o = out_ptr(*h, h->tout[0], x, cnt);
+      dopt::lhs_resolve(*h, k, static_cast<const double*>(pd[0]), o, trans != 0, info.data());
+      pinned_copy_out(*h, x, o, cnt);
     } else {
-      copy_out(*h, x, o, cnt);
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      staged_call(*h, 1, {{rhs, 0, cnt}}, {{x, 0, cnt}}, [&](const double** i, double** o) {
+        dopt::lhs_resolve(*h, k, i[0], o[0], trans != 0, info.data());
+      });
+      wait(*h);
     }
     h->last_time = tm.s();
     return 0;
@@ -1379,17 +1280,12 @@ int dopt_get_info(dopt_handle* h, int32_t* info) {
     if (h->kind == DOPT_KIND_QP && h->sparse) {   // LSQR only: never singular
       std::fill(info, info + h->batch, 0);
     } else if (h->kind == DOPT_KIND_QP) {
-      std::vector<dopt::QPMeta> meta(h->batch);
-      DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
-                                    hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      const std::vector<dopt::QPMeta> meta = read_meta(*h);
       for (int64_t i = 0; i < h->batch; ++i)
         info[i] = (meta[i].iterative || meta[i].info <= 0) ? 0 : full_column(*h, i, meta[i]);
     } else {
       if (!h->cinfo.p) throw Error(-1, "no conic solve has run");
-      DOPT_CHECK_HIP(hipMemcpyAsync(info, h->cinfo.p, h->batch * sizeof(int32_t),
-                                    hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      read_back(*h, info, h->cinfo.p, h->batch * sizeof(int32_t));
     }
     return 0;
   });
@@ -1406,7 +1302,7 @@ int dopt_qp_get_kept(dopt_handle* h, int8_t* kept) {
     if (B * m)
       DOPT_CHECK_HIP(hipMemcpyAsync(rpos.data(), h->kidx.as<int32_t>() + B * m, B * m * sizeof(int32_t),
                                     hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     for (size_t i = 0; i < B * m; ++i) kept[i] = rpos[i] >= 0;
     return 0;
   });
@@ -1426,10 +1322,7 @@ int dopt_qp_get_lu_kind(dopt_handle* h, int8_t* kinds) {
       std::fill(kinds, kinds + h->batch, (int8_t)DOPT_LU_KIND_LSQR);
       return 0;
     }
-    std::vector<dopt::QPMeta> meta(h->batch);
-    DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
-                                  hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    const std::vector<dopt::QPMeta> meta = read_meta(*h);
     for (int64_t i = 0; i < h->batch; ++i) {
       const auto& mm = meta[i];
       const int r = dopt::qp_route(mm.iterative, mm.nsys);
@@ -1450,10 +1343,7 @@ int dopt_qp_get_sym(dopt_handle* h, int8_t* flags) {
       std::fill(flags, flags + h->batch, (int8_t)0);
       return 0;
     }
-    std::vector<dopt::QPMeta> meta(h->batch);
-    DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
-                                  hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    const std::vector<dopt::QPMeta> meta = read_meta(*h);
     for (int64_t i = 0; i < h->batch; ++i) flags[i] = meta[i].sym && meta[i].lu == dopt::LU_NOPIV ? 1 : 0;
     return 0;
   });
@@ -1468,10 +1358,7 @@ int dopt_get_iterative(dopt_handle* h, int8_t* flags) {
       std::fill(flags, flags + h->batch, (int8_t)(h->sp_qnz ? 0 : 1));
       return 0;
     }
-    std::vector<dopt::QPMeta> meta(h->batch);
-    DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
-                                  hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    const std::vector<dopt::QPMeta> meta = read_meta(*h);
     for (int64_t i = 0; i < h->batch; ++i) flags[i] = (int8_t)meta[i].iterative;
     return 0;
   });
@@ -1487,16 +1374,11 @@ int dopt_get_system_size(dopt_handle* h, int32_t* sizes) {
         std::fill(sizes, sizes + h->batch, h->n + h->m + h->p);
         return 0;
       }
-      std::vector<dopt::QPMeta> meta(h->batch);
-      DOPT_CHECK_HIP(hipMemcpyAsync(meta.data(), h->meta.p, h->batch * sizeof(dopt::QPMeta),
-                                    hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      const std::vector<dopt::QPMeta> meta = read_meta(*h);
       for (int64_t i = 0; i < h->batch; ++i) sizes[i] = meta[i].nsys;
     } else {
       if (!h->cinfo.p) throw Error(-1, "no conic solve has run");
-      DOPT_CHECK_HIP(hipMemcpyAsync(sizes, h->cinfo.as<int32_t>() + h->batch,
-                                    h->batch * sizeof(int32_t), hipMemcpyDeviceToHost, h->stream));
-      DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+      read_back(*h, sizes, h->cinfo.as<int32_t>() + h->batch, h->batch * sizeof(int32_t));
     }
     return 0;
   });
@@ -1507,9 +1389,7 @@ int dopt_qp_lsqr_stats(dopt_handle* h, int32_t* stats) {
     if (h->kind != DOPT_KIND_QP || !h->sparse) throw Error(-1, "dopt_qp_lsqr_stats: sparse-route QP handles only");
     if (!stats) throw Error(-1, "stats is required");
     if (!h->sp_info.p) throw Error(-1, "no sparse solve has run");
-    DOPT_CHECK_HIP(hipMemcpyAsync(stats, h->sp_info.p, 4 * h->batch * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    read_back(*h, stats, h->sp_info.p, 4 * h->batch * sizeof(int32_t));
     return 0;
   });
 }
@@ -1587,7 +1467,7 @@ static void conic_set_common(Handle* h, const double* A, const double* b, const 
   h->cset = true;
   h->cfactored = false;
   h->conic_k = 0;
-  DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+  wait(*h);
 }
 
 int dopt_conic_set(dopt_handle* h, const double* A, const double* b, const double* c,
@@ -1637,11 +1517,7 @@ int dopt_conic_set_csc(dopt_handle* h, const int64_t* A_colptr, const int64_t* A
                                 d.as<double>(), h->csc_err.as<int>());
       A = d.as<double>();
     }
-    int herr = 0;
-    DOPT_CHECK_HIP(hipMemcpyAsync(&herr, h->csc_err.p, sizeof(int), hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
-    if (herr) throw Error(-1, (herr & 1) ? "CSC colptr is not monotone / out of range"
-                                         : "CSC rowval out of range");
+    if (const int herr = csc_err_read(*h)) throw Error(-1, csc_err_text(herr));
     conic_set_common(h, A, b, c, x, s, y, cone_desc, ncones);
     return 0;
   });
@@ -1651,7 +1527,7 @@ int dopt_conic_factor(dopt_handle* h) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_factor on a non-conic handle");
     dopt::conic_factor(*h);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    wait(*h);
     return 0;
   });
 }
@@ -1664,8 +1540,9 @@ int dopt_conic_forward(dopt_handle* h, const double* dA, const double* db, const
     if (!out) throw Error(-1, "out is required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    conic_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
-               [&](const double** i, double** o) { dopt::conic_forward(*h, i[0], i[1], i[2], o[0], o[1]); });
+    staged_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+                [&](const double** i, double** o) { dopt::conic_forward(*h, i[0], i[1], i[2], o[0], o[1]); });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1680,12 +1557,13 @@ int dopt_conic_forward_reverse(dopt_handle* h, const double* dA, const double* d
     if (!out || !dx || !out_g) throw Error(-1, "out, dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    conic_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
+    staged_call(*h, 1, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
                {{out, 0, B * N}, {out_dx, 1, B * n}, {out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m},
                 {out_dc, 5, B * n}},
-               [&](const double** i, double** o) {
+                [&](const double** i, double** o) {
                  dopt::conic_forward_reverse(*h, i[0], i[1], i[2], i[3], o[0], o[1], o[2], o[3], o[4], o[5]);
                });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1706,9 +1584,7 @@ int dopt_conic_lsqr_stats(dopt_handle* h, int32_t* stats) {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_lsqr_stats on a non-conic handle");
     if (!stats) throw Error(-1, "stats is required");
     if (!h->cinfo.p) throw Error(-1, "no conic solve has run");
-    DOPT_CHECK_HIP(hipMemcpyAsync(stats, h->cinfo.p, 4 * h->batch * sizeof(int32_t), hipMemcpyDeviceToHost,
-                                  h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    read_back(*h, stats, h->cinfo.p, 4 * h->batch * sizeof(int32_t));
     return 0;
   });
 }
@@ -1718,9 +1594,7 @@ int dopt_conic_lsqr_norms(dopt_handle* h, double* norms) {
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_lsqr_norms on a non-conic handle");
     if (!norms) throw Error(-1, "norms is required");
     if (!h->cnorm.p) throw Error(-1, "no conic solve has run");
-    DOPT_CHECK_HIP(hipMemcpyAsync(norms, h->cnorm.p, 8 * h->batch * sizeof(double), hipMemcpyDeviceToHost,
-                                  h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    read_back(*h, norms, h->cnorm.p, 8 * h->batch * sizeof(double));
     return 0;
   });
 }
@@ -1733,9 +1607,10 @@ int dopt_conic_reverse(dopt_handle* h, const double* dx, double* out_g, double* 
     if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    conic_call(*h, 1, {{dx, 0, B * n}},
+    staged_call(*h, 1, {{dx, 0, B * n}},
                {{out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
-               [&](const double** i, double** o) { dopt::conic_reverse(*h, i[0], o[0], o[1], o[2], o[3]); });
+                [&](const double** i, double** o) { dopt::conic_reverse(*h, i[0], o[0], o[1], o[2], o[3]); });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });
@@ -1750,9 +1625,10 @@ int dopt_conic_reverse_k(dopt_handle* h, int32_t k, const double* dx, double* ou
     if (!dx || !out_g) throw Error(-1, "dx and out_g are required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    conic_call(*h, k, {{dx, 0, B * n}},
+    staged_call(*h, k, {{dx, 0, B * n}},
                {{out_g, 2, B * N}, {out_dA, 3, B * m * n}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
-               [&](const double** i, double** o) { dopt::conic_reverse_k(*h, k, i[0], o[0], o[1], o[2], o[3]); });
+                [&](const double** i, double** o) { dopt::conic_reverse_k(*h, k, i[0], o[0], o[1], o[2], o[3]); });
+    wait(*h);
     h->conic_k = k;
     h->last_time = tm.s();
     return 0;
@@ -1768,8 +1644,9 @@ int dopt_conic_forward_k(dopt_handle* h, int32_t k, const double* dA, const doub
     if (!out) throw Error(-1, "out is required");
     Timer tm;
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
-    conic_call(*h, k, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
-               [&](const double** i, double** o) { dopt::conic_forward_k(*h, k, i[0], i[1], i[2], o[0], o[1]); });
+    staged_call(*h, k, {{dA, 1, B * m * n}, {db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+                [&](const double** i, double** o) { dopt::conic_forward_k(*h, k, i[0], i[1], i[2], o[0], o[1]); });
+    wait(*h);
     h->conic_k = k;
     h->last_time = tm.s();
     return 0;
@@ -1800,12 +1677,13 @@ int dopt_conic_forward_csc(dopt_handle* h, const int64_t* dA_colptr, const int64
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
     const bool sp = conic_stage_tangent(*h, dA_colptr, dA_rowval, dA_nzval, dA_nnz);
     int herr = 0;
-    conic_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
-               [&](const double** i, double** o) {
+    staged_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}}, {{out, 0, B * N}, {out_dx, 1, B * n}},
+                [&](const double** i, double** o) {
                  if (sp) dopt::conic_forward_csc(*h, h->spt[0], h->csc_err.as<int>(), i[0], i[1], o[0], o[1]);
                  else dopt::conic_forward(*h, nullptr, i[0], i[1], o[0], o[1]);
                  if (sp) csc_err_queue(*h, &herr);
                });
+    wait(*h);
     csc_err_raise(herr);
     h->last_time = tm.s();
     return 0;
@@ -1824,9 +1702,9 @@ int dopt_conic_forward_reverse_csc(dopt_handle* h, const int64_t* dA_colptr, con
     const size_t B = h->batch, n = h->n, m = h->m, N = n + m + 1;
     const bool sp = conic_stage_tangent(*h, dA_colptr, dA_rowval, dA_nzval, dA_nnz);
     int herr = 0;
-    conic_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
+    staged_call(*h, 1, {{db, 2, B * m}, {dc, 3, B * n}, {dx, 0, B * n}},
                {{out, 0, B * N}, {out_dx, 1, B * n}, {out_g, 2, B * N}, {out_db, 4, B * m}, {out_dc, 5, B * n}},
-               [&](const double** i, double** o) {
+                [&](const double** i, double** o) {
                  if (sp)
                    dopt::conic_forward_reverse_csc(*h, h->spt[0], h->csc_err.as<int>(), i[0], i[1], i[2], o[0], o[1],
                                                    o[2], o[3], o[4]);
@@ -1834,6 +1712,7 @@ int dopt_conic_forward_reverse_csc(dopt_handle* h, const int64_t* dA_colptr, con
                    dopt::conic_forward_reverse(*h, nullptr, i[0], i[1], i[2], o[0], o[1], o[2], nullptr, o[3], o[4]);
                  if (sp) csc_err_queue(*h, &herr);
                });
+    wait(*h);
     csc_err_raise(herr);
     h->last_time = tm.s();
     return 0;
@@ -1848,11 +1727,9 @@ int dopt_conic_reverse_grads_csc(dopt_handle* h, const double* g, const int64_t*
     const size_t B = h->batch, N = (size_t)h->n + h->m + 1;
     const dopt::CscArg P = stage_csc(*h, 0, P_colptr, P_rowval, nullptr, P_nnz, false);
     const size_t cnt = P.cp ? (size_t)P.nnz : h->sparse ? (size_t)h->sp[0].nnz : 0;   // (refusals: conic_reverse_grads_at)
-    const double* gd = stage_in(*h, h->tin[0], g, B * N);
-    double* o = nz_out_ptr(*h, h->tout[3], out_nz, cnt);
-    int* err = csc_err_clear(*h);
-    dopt::conic_reverse_grads_at(*h, gd, P, o, err);
-    copy_out(*h, out_nz, o, cnt);
+    staged_call(*h, 1, {{g, 0, B * N}}, {{out_nz, 3, cnt, true}}, [&](const double** i, double** o) {
+      dopt::conic_reverse_grads_at(*h, i[0], P, o[0], csc_err_clear(*h));
+    });
     csc_err_wait(*h);
     return 0;
   });
@@ -1865,9 +1742,7 @@ int dopt_conic_lsqr_stats_k(dopt_handle* h, int32_t k, int32_t* stats) {
     if (k < 1) throw Error(-1, "dopt_conic_lsqr_stats_k: k must be at least 1");
     if (h->conic_k != k || !h->cinfok.p)
       throw Error(-1, "dopt_conic_lsqr_stats_k: the last conic call was not a _k call with this k");
-    DOPT_CHECK_HIP(hipMemcpyAsync(stats, h->cinfok.p, (size_t)2 * h->batch * k * sizeof(int32_t),
-                                  hipMemcpyDeviceToHost, h->stream));
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    read_back(*h, stats, h->cinfok.p, (size_t)2 * h->batch * k * sizeof(int32_t));
     return 0;
   });
 }
@@ -1881,13 +1756,11 @@ int dopt_conic_params_forward(dopt_handle* h, const double* dp, int32_t nparam, 
     if ((nparam > 0 && !dp) || (h->m && !db) || (h->n && !dc))
       throw Error(-1, "dp, db (m > 0) and dc (n > 0) are required");
     const size_t B = h->batch, n = h->n, m = h->m, P = nparam > 0 ? (size_t)nparam : 0;
-    const double* d = P ? stage_in(*h, h->tin[0], dp, B * P) : nullptr;
-    double* ob = m ? out_ptr(*h, h->tout[4], db, B * m) : nullptr;
-    double* oc = n ? out_ptr(*h, h->tout[5], dc, B * n) : nullptr;
-    dopt::conic_params_forward(*h, d, nparam, nterms, t_param, t_kind, t_index, t_coef, ob, oc);
-    if (m) copy_out(*h, db, ob, B * m);
-    if (n) copy_out(*h, dc, oc, B * n);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{P ? dp : nullptr, 0, B * P}}, {{m ? db : nullptr, 4, B * m}, {n ? dc : nullptr, 5, B * n}},
+                [&](const double** i, double** o) {
+                  dopt::conic_params_forward(*h, i[0], nparam, nterms, t_param, t_kind, t_index, t_coef, o[0], o[1]);
+                });
+    wait(*h);
     return 0;
   });
 }
@@ -1899,11 +1772,10 @@ int dopt_conic_params_reverse(dopt_handle* h, const double* g, int32_t nparam, i
     if (h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_conic_params_reverse on a non-conic handle");
     if (!g || (nparam > 0 && !out_dp)) throw Error(-1, "g and out_dp are required");
     const size_t B = h->batch, N = (size_t)h->n + h->m + 1, P = nparam > 0 ? (size_t)nparam : 0;
-    const double* gd = stage_in(*h, h->tin[0], g, B * N);
-    double* o = P ? out_ptr(*h, h->tout[0], out_dp, B * P) : nullptr;
-    dopt::conic_params_reverse(*h, gd, nparam, nterms, t_param, t_kind, t_index, t_coef, o);
-    if (P) copy_out(*h, out_dp, o, B * P);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {{g, 0, B * N}}, {{P ? out_dp : nullptr, 0, B * P}}, [&](const double** i, double** o) {
+      dopt::conic_params_reverse(*h, i[0], nparam, nterms, t_param, t_kind, t_index, t_coef, o[0]);
+    });
+    wait(*h);
     return 0;
   });
 }
@@ -1917,10 +1789,10 @@ int dopt_conic_params_jacobian(dopt_handle* h, int32_t mode, int32_t nparam, int
     const size_t cnt = (size_t)h->batch * h->n * (nparam > 0 ? (size_t)nparam : 0);
     if (cnt && !out_J) throw Error(-1, "out_J is required");
     Timer tm;
-    double* o = cnt ? out_ptr(*h, h->tout[0], out_J, cnt) : nullptr;
-    dopt::conic_params_jacobian(*h, mode, nparam, nterms, t_param, t_kind, t_index, t_coef, o, stats);
-    if (cnt) copy_out(*h, out_J, o, cnt);
-    DOPT_CHECK_HIP(hipStreamSynchronize(h->stream));
+    staged_call(*h, 1, {}, {{cnt ? out_J : nullptr, 0, cnt}}, [&](const double**, double** o) {
+      dopt::conic_params_jacobian(*h, mode, nparam, nterms, t_param, t_kind, t_index, t_coef, o[0], stats);
+    });
+    wait(*h);
     h->last_time = tm.s();
     return 0;
   });

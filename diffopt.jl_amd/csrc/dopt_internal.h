@@ -2,6 +2,7 @@
 #pragma once
 #include <hip/hip_runtime.h>
 
+#include <atomic>
 #include <cstdint>
 #include <functional>
 #include <string>
@@ -25,26 +26,61 @@ struct Error {
   Error(int c, std::string m) : code(c), msg(std::move(m)) {}
 };
 
-// Device buffer owned by a handle.
+// Bytes of device memory the process's DevBufs hold (dopt_live_device_bytes).
+inline std::atomic<int64_t> live_device_bytes{0};
+
+// Device buffer owned by a handle: freed with it.  Not copyable, so nothing
+// can hold one (or a struct of them) by value beside its owner.
 struct DevBuf {
   void* p = nullptr;
   size_t bytes = 0;
+  DevBuf() = default;
+  DevBuf(const DevBuf&) = delete;
+  DevBuf& operator=(const DevBuf&) = delete;
+  ~DevBuf() { release(); }
   void ensure(size_t nbytes) {
     if (nbytes <= bytes && p) return;
-    if (p) (void)hipFree(p);
-    p = nullptr;
-    bytes = 0;
+    release();
     if (nbytes == 0) return;
     DOPT_CHECK_HIP(hipMalloc(&p, nbytes));
     bytes = nbytes;
+    live_device_bytes += (int64_t)nbytes;
   }
   void release() {
-    if (p) (void)hipFree(p);
+    if (!p) return;
+    (void)hipFree(p);
+    live_device_bytes -= (int64_t)bytes;
     p = nullptr;
     bytes = 0;
   }
   template <class T>
   T* as() const { return static_cast<T*>(p); }
+};
+
+// Pinned host buffer owned by a handle, with its device address (the small
+// path's kernels read and write it in place).  grow() keeps no contents.
+struct PinBuf {
+  char* p = nullptr;
+  char* dev = nullptr;
+  size_t bytes = 0;
+  PinBuf() = default;
+  PinBuf(const PinBuf&) = delete;
+  PinBuf& operator=(const PinBuf&) = delete;
+  ~PinBuf() {
+    if (p) (void)hipHostFree(p);
+  }
+  char* grow(size_t nbytes) {
+    if (nbytes <= bytes) return p;
+    if (p) DOPT_CHECK_HIP(hipHostFree(p));
+    p = dev = nullptr;
+    bytes = 0;
+    DOPT_CHECK_HIP(hipHostMalloc((void**)&p, nbytes, hipHostMallocDefault));
+    bytes = nbytes;
+    void* d = nullptr;
+    DOPT_CHECK_HIP(hipHostGetDevicePointer(&d, p, 0));
+    dev = static_cast<char*>(d);
+    return p;
+  }
 };
 
 // Per-problem QP metadata (device, batch entries).
@@ -167,23 +203,20 @@ struct Handle {
   DevBuf own_in[7];          // host-mode copies of the 7 QP inputs (Q, G, A: also the CSC densification)
   // small host-mode inputs gathered into one pinned buffer and moved by ONE
   // copy (dopt_qp_set_csc of a batch-1 model: 13 copies → 1)
-  void* pin = nullptr;
-  size_t pin_bytes = 0;
+  PinBuf pin;
   // dopt_qp_set_csc of a small host-mode model returns with its copy out of
   // `pin` queued (validated on the host, nothing to read back): the next
   // pack waits for this event before it writes the buffer again
   hipEvent_t pin_ev = nullptr;
   bool pin_pending = false;
   DevBuf pack;
-  // the small path's per-call traffic (abi.hip): the tangents packed like the
-  // inputs (into tpack: pack stays the inputs' home), the outputs and the
-  // per-problem flags read back by ONE copy into pin_out
+  // the small path's per-call traffic (abi.hip small_io): the tangents packed
+  // like the inputs (into tpack: pack stays the inputs' home), the outputs and
+  // the per-problem flags written into pin_out in place
   DevBuf tpack;
   DevBuf rpack;              // dopt_lhs_resolve's right-hand sides (tpack may hold the plug point's M)
-  void* pin_out = nullptr;
-  char* pin_out_dev = nullptr;   // its device address (the small path's kernels read / write it directly)
-  size_t pin_out_bytes = 0;
-  int io_calls = 0;          // small-path calls so far (abi.hip pin_ok: pinned from the third on)
+  PinBuf pin_out;
+  int io_calls = 0;          // small-path and plug-point calls so far (abi.hip use_pinned: pinned from the third on)
   DevBuf csc_in[9], csc_in_val[3], csc_err;   // host-mode copies of CSC colptr / rowval / nzval
   int32_t nmax = 0, ld = 0;  // max system size, K row stride (doubles)
   DevBuf K, ipiv, s, kidx, meta, rhs, x;
@@ -294,6 +327,7 @@ struct Handle {
 
   // scratch for host-mode tangents / outputs
   DevBuf tin[8], tout[6];
+  DevBuf pterms;             // the params calls' term table (params.hip DevCsr)
 
   // per-phase GPU timing (HIP events on the handle's stream)
   uint32_t prof = 0;   // phases timed (bit DOPT_PHASE_x)

@@ -214,17 +214,18 @@ Csr csr_by(int rows, int64_t nterms, const std::vector<int32_t>& key, const int3
   return c;
 }
 
-// the CSR arrays in device memory (one allocation per call)
+// the CSR arrays in the handle's term-table buffer (h.pterms grows like every
+// staging buffer).  The copies read `c`: every caller waits for the stream
+// before `c` goes out of scope.
 struct DevCsr {
-  DevBuf buf;
   int64_t* ptr = nullptr;
   int32_t *kind = nullptr, *index = nullptr, *param = nullptr;
   double* coef = nullptr;
-  DevCsr(const Csr& c, hipStream_t st) {
+  DevCsr(Handle& h, const Csr& c) {
+    const hipStream_t st = h.stream;
     const size_t nt = c.coef.size(), np = c.ptr.size();
-    const size_t bytes = np * 8 + nt * 8 + 3 * nt * 4 + 64;
-    buf.ensure(bytes);
-    char* p = static_cast<char*>(buf.p);
+    h.pterms.ensure(np * 8 + nt * 8 + 3 * nt * 4 + 64);
+    char* p = h.pterms.as<char>();
     ptr = reinterpret_cast<int64_t*>(p);
     coef = reinterpret_cast<double*>(p + np * 8);
     kind = reinterpret_cast<int32_t*>(p + np * 8 + nt * 8);
@@ -249,13 +250,13 @@ void qp_params_reverse(Handle& h, const double* rev, int nparam, int64_t nterms,
   if (nparam == 0) return;
   std::vector<int32_t> key(t_param, t_param + nterms);
   const Csr c = csr_by(nparam, nterms, key, t_param, t_kind, t_index, t_coef);
-  DevCsr d(c, h.stream);
+  DevCsr d(h, c);
   static const double dummy = 0.0;
   hipLaunchKernelGGL(poi_reverse_kernel, dim3((nparam + PTPB - 1) / PTPB, (unsigned)h.batch), dim3(PTPB), 0,
                      h.stream, rev, h.m ? h.lam : &dummy, h.n, h.m, h.p, nparam, d.ptr, d.kind, d.index, d.coef,
                      out);
   DOPT_CHECK_HIP(hipGetLastError());
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the staging buffer dies with `d`
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
 }
 
 void qp_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
@@ -283,7 +284,7 @@ void qp_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, 
     c2[u] = t_coef[keep[u]];
   }
   const Csr c = csr_by(rows, (int64_t)keep.size(), kk, p2.data(), k2.data(), i2.data(), c2.data());
-  DevCsr d(c, h.stream);
+  DevCsr d(h, c);
   static double dummy = 0.0;
   hipLaunchKernelGGL(poi_forward_kernel, dim3((rows + PTPB - 1) / PTPB, (unsigned)h.batch), dim3(PTPB), 0,
                      h.stream, dp, std::max(nparam, 1), h.n, h.m, h.p, d.ptr, d.param, d.coef, dq,
@@ -363,12 +364,12 @@ void conic_params_forward(Handle& h, const double* dp, int nparam, int64_t nterm
   if (!h.cset) throw Error(-1, "dopt_conic_params_forward: dopt_conic_set has not been called");
   validate_conic(h, nparam, nterms, t_param, t_kind, t_index, t_coef);
   const Csr c = conic_forward_csr(h, nterms, t_param, t_kind, t_index, t_coef);
-  DevCsr d(c, h.stream);
+  DevCsr d(h, c);
   {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_RHS);
     launch_conic_forward(h, d, dp, 0, nparam, h.batch, db, dc);
   }
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the staging buffer dies with `d`
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
 }
 
 void conic_params_reverse(Handle& h, const double* g, int nparam, int64_t nterms, const int32_t* t_param,
@@ -379,7 +380,7 @@ void conic_params_reverse(Handle& h, const double* g, int nparam, int64_t nterms
   if (!h.cfactored) conic_factor(h);   // x and vp
   std::vector<int32_t> key(t_param, t_param + nterms);
   const Csr c = csr_by(nparam, nterms, key, t_param, t_kind, t_index, t_coef);
-  DevCsr d(c, h.stream);
+  DevCsr d(h, c);
   {
     PhaseTimer pt(h, DOPT_PHASE_CONIC_OUTPUT);
     launch_conic_reverse(h, d, g, nparam, h.batch, out);
@@ -412,7 +413,7 @@ void conic_params_jacobian(Handle& h, int mode, int nparam, int64_t nterms, cons
   Csr c;
   if (mode == 0) c = conic_forward_csr(h, nterms, t_param, t_kind, t_index, t_coef);
   else c = csr_by(nparam, nterms, std::vector<int32_t>(t_param, t_param + nterms), t_param, t_kind, t_index, t_coef);
-  DevCsr d(c, h.stream);
+  DevCsr d(h, c);
   for (int s0 = 0; s0 < seeds; s0 += chunk) {
     const int k = std::min(chunk, seeds - s0);
     const int64_t cols = (int64_t)k * (int64_t)B;
@@ -439,7 +440,7 @@ void conic_params_jacobian(Handle& h, int mode, int nparam, int64_t nterms, cons
       DOPT_CHECK_HIP(hipMemcpyAsync(stats + (size_t)2 * B * s0, h.cinfok.p, (size_t)2 * B * k * sizeof(int32_t),
                                     hipMemcpyDeviceToHost, h.stream));
   }
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the staging buffer dies with `d`
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
 }
 
 }  // namespace dopt

@@ -36,6 +36,7 @@ _h = ctypes.c_void_p
 # symbol → (restype, argtypes); must match include/diffopt_mi355x.h exactly
 SIGNATURES = {
     "dopt_abi_version": (ctypes.c_int, []),
+    "dopt_live_device_bytes": (ctypes.c_int64, []),
     "dopt_create": (ctypes.c_int, [ctypes.POINTER(_h), ctypes.c_int, ctypes.c_int64,
                                    ctypes.c_int32, ctypes.c_int32, ctypes.c_int32,
                                    ctypes.c_int32]),

@@ -72,6 +72,11 @@ int dopt_create(dopt_handle** h, int device, int64_t batch, int32_t n,
 int dopt_destroy(dopt_handle* h);
 const char* dopt_last_error(const dopt_handle* h);
 int dopt_abi_version(void);
+/* Test and diagnostic aid: the bytes of device memory that all of this
+ * process's handles own at the moment (every device, staging and workspace
+ * buffers included; pinned host memory, streams and events are not counted).
+ * A handle's share returns to zero with dopt_destroy. */
+int64_t dopt_live_device_bytes(void);
 /* hipStream_t as void*; NULL = the legacy default (null) stream.  Until this
  * is called the handle uses a private non-blocking stream.  A caller that
  * produces device-mode inputs on stream S passes S here (PyTorch: the current
