@@ -815,6 +815,52 @@ int dopt_qp_forward_k(dopt_handle* h, int32_t k, const double* dQ, const double*
   });
 }
 
+// The parameter calls on k seeds (params.hip): right-hand sides from the term table, the _k solves
+int dopt_qp_params_forward_k(dopt_handle* h, int32_t k, const double* dp, int32_t nparam, int64_t nterms,
+                             const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                             const int32_t* t_var, const double* t_coef, double* out) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_params_forward_k on a non-QP handle");
+    if (h->sparse) throw Error(-1, "multi-RHS calls need factors: not on the sparse (LSQR) route");
+    if (k < 0) throw Error(-1, "k must not be negative");
+    if (!dp && k != nparam) throw Error(-1, "dopt_qp_params_forward_k: unit seeds (dp == NULL) need k == nparam");
+    Timer tm;
+    const size_t B = h->batch, L = (size_t)h->n + h->m + h->p, P = nparam > 0 ? (size_t)nparam : 0;
+    const bool work = P && k && B;
+    staged_call(*h, k, {{work ? dp : nullptr, 0, B * P}}, {{work ? out : nullptr, 1, B * L}},
+                [&](const double** i, double** o) {
+                  dopt::qp_params_forward_k(*h, k, i[0], nparam, nterms, t_param, t_kind, t_index, t_var, t_coef,
+                                            o[0]);
+                });
+    const int rc = work ? first_info(*h) : 0;
+    h->last_time = tm.s();
+    return rc;
+  });
+}
+
+int dopt_qp_params_reverse_k(dopt_handle* h, int32_t k, const double* dl_dz, int32_t nparam, int64_t nterms,
+                             const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                             const int32_t* t_var, const double* t_coef, double* out_rev, double* out_dp) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_params_reverse_k on a non-QP handle");
+    if (h->sparse) throw Error(-1, "multi-RHS calls need factors: not on the sparse (LSQR) route");
+    if (k < 0) throw Error(-1, "k must not be negative");
+    if (!dl_dz && k != h->n) throw Error(-1, "dopt_qp_params_reverse_k: unit seeds (dl_dz == NULL) need k == n");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, L = n + h->m + h->p, P = nparam > 0 ? (size_t)nparam : 0;
+    const bool work = P && k && B;
+    staged_call(*h, k, {{work ? dl_dz : nullptr, 0, B * n}},
+                {{work ? out_rev : nullptr, 0, B * L}, {work ? out_dp : nullptr, 1, B * P}},
+                [&](const double** i, double** o) {
+                  dopt::qp_params_reverse_k(*h, k, i[0], nparam, nterms, t_param, t_kind, t_index, t_var, t_coef,
+                                            o[0], o[1]);
+                });
+    const int rc = work ? first_info(*h) : 0;
+    h->last_time = tm.s();
+    return rc;
+  });
+}
+
 int dopt_qp_forward_reverse(dopt_handle* h, const double* dl_dz, const double* dQ,
                             const double* dq, const double* dG, const double* dh,
                             const double* dA, const double* db, double* out_rev,

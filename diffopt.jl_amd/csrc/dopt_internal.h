@@ -328,6 +328,7 @@ struct Handle {
   // scratch for host-mode tangents / outputs
   DevBuf tin[8], tout[6];
   DevBuf pterms;             // the params calls' term table (params.hip DevCsr)
+  DevBuf qjac;               // dopt_qp_params_reverse_k without out_rev: a chunk's reverse outputs
 
   // per-phase GPU timing (HIP events on the handle's stream)
   uint32_t prof = 0;   // phases timed (bit DOPT_PHASE_x)
@@ -458,6 +459,16 @@ void qp_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, 
                        double* dh, double* db);
 void qp_forward_k(Handle& h, int k, const double* dQ, const double* dq, const double* dG, const double* dh,
                   const double* dA, const double* db, double* out);
+// k right-hand sides already in rk (reduced; fk: the full forward copies, null for trans 0) through the multi-RHS
+// solve, the generic / LSQR routes per seed and qp_output_k_kernel (qp.hip); rk / xk / fk: seed-major, stride B·nmax
+void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out);
+// QP parameter calls on k seeds (params.hip): right-hand sides straight from the term table, then solve_k
+void qp_params_forward_k(Handle& h, int k, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
+                         const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
+                         double* out);
+void qp_params_reverse_k(Handle& h, int k, const double* dl_dz, int nparam, int64_t nterms, const int32_t* t_param,
+                         const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
+                         double* out_rev, double* out_dp);
 void qp_blocked_solve2(Handle& h, const double* dinv, const double* rhs_rev, const double* rhs_fwd,
                        double* x_rev, double* x_fwd, int sel, const double* w_rev = nullptr,
                        const double* w_fwd = nullptr);

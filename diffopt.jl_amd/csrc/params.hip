@@ -22,6 +22,11 @@
 //   The objective's constant tangent does not enter the KKT system.
 // Each sum runs over its terms in the order the caller lists them (the
 // reference's accumulation order when the caller preserves it).
+// The `_k` calls ("QP parameter calls on k seeds" below) add
+//   kind 4  parameter×variable term (p, v) of LessThan row i  (ParametricQuadraticFunction
+//   kind 5  parameter×variable term (p, v) of EqualTo row i    constraints, :147-203, :390-441)
+// whose forward tangent is dG[i, v] / dA[i, v] += dp[p] · c and whose reverse
+// getter is the coefficient of v in ReverseConstraintFunction(ci).
 #include "dopt_internal.h"
 
 #include <algorithm>
@@ -72,6 +77,177 @@ __global__ __launch_bounds__(PTPB) void poi_forward_kernel(const double* __restr
   if (r < m) dh[(size_t)b * m + r] = -acc;
   else if (r < m + p) db[(size_t)b * p + (r - m)] = -acc;
   else dq[(size_t)b * n + (r - m - p)] = acc;
+}
+
+// ---------------------------------------------------------------------------
+// QP parameter calls on k seeds (dopt_qp_params_forward_k / _reverse_k).  A
+// column is one (seed, problem) pair, seed-major: column c = seed·B + b works
+// on problem b = c mod B; work vectors at + c·nmax, outputs at + c·(n+m+p).
+// ---------------------------------------------------------------------------
+// The tangent of term (param, coef) in column c: dp·c, or for the unit seeds
+// (dp == null) the same product on the unit vector of parameter `unit`.
+__device__ __forceinline__ double poi_dt(const double* __restrict__ dp, size_t c, int nparam, int unit, int param,
+                                         double coef) {
+  return (dp ? dp[c * nparam + param] : (param == unit ? 1.0 : 0.0)) * coef;
+}
+
+// λ·a − λ·b with both products rounded, as Julia's λ.*(dG z) − λ.*dh rounds
+// them (no contraction into an FMA): equal a and b cancel exactly, so a
+// direction the problem does not move along gives an exactly zero entry.
+__device__ __forceinline__ double lam_diff(double l, double a, double b) {
+#pragma clang fp contract(off)
+  return l * a - l * b;
+}
+
+// Forward right-hand sides of a chunk of seeds, straight from the term table
+// (parameters.jl:91-300 into QuadraticProgram.jl:429-433): what
+// qp_fwd_rhs_kernel (qp.hip) writes from the dense tangents the terms define —
+// dq_v = Σ d (kind 3), dh_i = −Σ d (kind 0), db_e = −Σ d (kind 1),
+// dG[i,v] = Σ d (kind 4), dA[e,v] = Σ d (kind 5), d = dp·c — with its
+// expression shapes (the transposed products added to dq one after the other,
+// λ·(dG z) − λ·dh, dA z − db), and both of its copies: the full-length one
+// (`full`; the output kernel recovers an eliminated row's x_λ as r_i/s_i from
+// it) and the reduced one (`rhs`, through rpos and meta.nk).  One thread per
+// (row, column); rows [0, nmax): every entry of both copies is written (zeros
+// past n+m+p and past the reduced size), the buffers being reused between
+// calls.  Two CSRs over the terms, each stable in the caller's order: `r*` by
+// constraint row (m LessThan rows, then p EqualTo rows; kinds 0, 1, 4, 5),
+// `v*` by variable (kinds 3, 4, 5; `vindex` the term's row).
+__global__ __launch_bounds__(PTPB) void qp_poi_fwd_rhs_kernel(
+    const double* __restrict__ dp, int p0, int nparam, int n, int m, int p, int nmax, int B, int64_t cols,
+    const int64_t* __restrict__ rptr, const int32_t* __restrict__ rkind, const int32_t* __restrict__ rparam,
+    const int32_t* __restrict__ rvar, const double* __restrict__ rcoef, const int64_t* __restrict__ vptr,
+    const int32_t* __restrict__ vkind, const int32_t* __restrict__ vparam, const int32_t* __restrict__ vindex,
+    const double* __restrict__ vcoef, const double* __restrict__ z, const double* __restrict__ lam,
+    const double* __restrict__ nu, const int32_t* __restrict__ rpos, const QPMeta* __restrict__ meta,
+    double* __restrict__ full, double* __restrict__ rhs) {
+  const int r = blockIdx.x * PTPB + threadIdx.x;
+  if (r >= nmax) return;
+  const int L = n + m + p;
+  int64_t t0 = 0, t1 = 0;
+  if (r < n) {
+    t0 = vptr[r];
+    t1 = vptr[r + 1];
+  } else if (r < L) {
+    t0 = rptr[r - n];
+    t1 = rptr[r - n + 1];
+  }
+  for (int64_t c = blockIdx.y; c < cols; c += gridDim.y) {
+    const int b = (int)(c % B), unit = p0 + (int)(c / B);
+    const double* zb = z + (size_t)b * n;
+    const double* lb = lam + (size_t)b * m;
+    const double* nb = nu + (size_t)b * p;
+    double val = 0.0;
+    int dst = -1;   // the entry's place in the reduced system (−1: an eliminated row, or padding)
+    if (r < n) {
+      // r1 = dq + dGᵀλ + dAᵀν
+      double aq = 0.0, ag = 0.0, aa = 0.0;
+      for (int64_t t = t0; t < t1; ++t) {
+        const double d = poi_dt(dp, (size_t)c, nparam, unit, vparam[t], vcoef[t]);
+        const int k = vkind[t];
+        if (k == 3) aq += d;
+        else if (k == 4) ag = fma(d, lb[vindex[t]], ag);
+        else aa = fma(d, nb[vindex[t]], aa);
+      }
+      val = aq;
+      val += ag;
+      val += aa;
+      dst = r;
+    } else if (r < n + m) {
+      // r2 = λ.*(dG z) − λ.*dh
+      const int l = r - n;
+      double gz = 0.0, cte = 0.0;
+      for (int64_t t = t0; t < t1; ++t) {
+        const double d = poi_dt(dp, (size_t)c, nparam, unit, rparam[t], rcoef[t]);
+        if (rkind[t] == 4) gz = fma(d, zb[rvar[t]], gz);
+        else cte += d;
+      }
+      const double hh = -cte;
+      val = lam_diff(lb[l], gz, hh);
+      const int kk = rpos[(size_t)b * m + l];
+      if (kk >= 0) dst = n + kk;
+    } else if (r < L) {
+      // r3 = dA z − db
+      double az = 0.0, cte = 0.0;
+      for (int64_t t = t0; t < t1; ++t) {
+        const double d = poi_dt(dp, (size_t)c, nparam, unit, rparam[t], rcoef[t]);
+        if (rkind[t] == 5) az = fma(d, zb[rvar[t]], az);
+        else cte += d;
+      }
+      val = az - (-cte);
+      dst = n + meta[b].nk + (r - n - m);
+    }
+    full[(size_t)c * nmax + r] = val;
+    if (dst >= 0) rhs[(size_t)c * nmax + dst] = val;   // dst < nsys: no two threads share an entry
+    if (r >= meta[b].nsys) rhs[(size_t)c * nmax + r] = 0.0;
+  }
+}
+
+// Reverse right-hand sides of a chunk of seeds: [dl_dz; 0] of the column
+// (what qp_rev_rhs_kernel, qp.hip, writes), or for the unit seeds (dl_dz ==
+// null) e_{v0 + seed}.  Rows [0, nmax): no stale entry.
+__global__ __launch_bounds__(PTPB) void qp_poi_rev_rhs_kernel(const double* __restrict__ dl_dz, int v0, int n,
+                                                              int nmax, int B, int64_t cols,
+                                                              double* __restrict__ rhs) {
+  const int i = blockIdx.x * PTPB + threadIdx.x;
+  if (i >= nmax) return;
+  for (int64_t c = blockIdx.y; c < cols; c += gridDim.y) {
+    double v = 0.0;
+    if (i < n) v = dl_dz ? dl_dz[(size_t)c * n + i] : (i == v0 + (int)(c / B) ? 1.0 : 0.0);
+    rhs[(size_t)c * nmax + i] = v;
+  }
+}
+
+// Reverse accumulation over the columns (parameters.jl:341-534): one thread
+// per (column, parameter), out[c·nparam + r] = Σ_t c_t·s_t over the
+// parameter's terms in the caller's order, from the column's full reverse
+// output rev = [dz | dλ | dν] (qp_output_k_kernel's, the eliminated rows' dλ
+// included).  Kinds 0-3 as poi_reverse_kernel.  Kinds 4 and 5 read the
+// coefficient of v in ReverseConstraintFunction(ci) (:390-441): the entry
+// expressions restate qp_reverse_grads_kernel's dG / dA (qp.hip) — change
+// them together:
+//   kind 4  s = λ_i·dλ_i·z_v + λ_i·dz_v
+//   kind 5  s = dν_i·z_v + ν_i·dz_v
+__global__ __launch_bounds__(PTPB) void qp_poi_reverse_k_kernel(
+    const double* __restrict__ rev, const double* __restrict__ z, const double* __restrict__ lam,
+    const double* __restrict__ nu, int n, int m, int p, int B, int64_t cols, int nparam,
+    const int64_t* __restrict__ ptr, const int32_t* __restrict__ kind, const int32_t* __restrict__ index,
+    const int32_t* __restrict__ var, const double* __restrict__ coef, double* __restrict__ out) {
+  const int r = blockIdx.x * PTPB + threadIdx.x;
+  if (r >= nparam) return;
+  const int L = n + m + p;
+  const int64_t t0 = ptr[r], t1 = ptr[r + 1];
+  for (int64_t c = blockIdx.y; c < cols; c += gridDim.y) {
+    const int b = (int)(c % B);
+    const double* rb = rev + (size_t)c * L;
+    const double* zb = z + (size_t)b * n;
+    const double* lb = lam + (size_t)b * m;
+    const double* nb = nu + (size_t)b * p;
+    double acc = 0.0;
+    for (int64_t t = t0; t < t1; ++t) {
+      const int i = index[t];
+      double s;
+      switch (kind[t]) {
+        case 0: s = lb[i] * rb[n + i]; break;   // λ_i·dλ_i
+        case 1: s = rb[n + m + i]; break;       // dν_i
+        case 3: s = rb[i]; break;               // dz_v
+        case 4: {
+          const int j = var[t];
+          const double li = lb[i];
+          s = li * rb[n + i] * zb[j] + li * rb[j];
+          break;
+        }
+        case 5: {
+          const int j = var[t];
+          s = rb[n + m + i] * zb[j] + nb[i] * rb[j];
+          break;
+        }
+        default: s = 0.0; break;                // objective constant
+      }
+      acc += coef[t] * s;
+    }
+    out[(size_t)c * nparam + r] = acc;
+  }
 }
 
 // ---------------------------------------------------------------------------
@@ -163,18 +339,26 @@ __global__ __launch_bounds__(PTPB) void conic_unit_seed_kernel(int v0, int n, in
 struct Csr {
   std::vector<int64_t> ptr;
   std::vector<int32_t> kind, index, param;
+  std::vector<int32_t> var;   // kinds 4 and 5: the term's variable (the _k calls; empty otherwise)
   std::vector<double> coef;
 };
 
+// t_var: the variables of the constraints' parameter×variable terms (kinds 4: LessThan row, 5: EqualTo row), which
+// only the _k calls take (pv); without pv kinds above 3 are out of range
 void validate(const Handle& h, int nparam, int64_t nterms, const int32_t* t_param, const int32_t* t_kind,
-              const int32_t* t_index, const double* t_coef) {
+              const int32_t* t_index, const double* t_coef, const int32_t* t_var = nullptr, bool pv = false) {
   if (nparam < 0 || nterms < 0) throw Error(-1, "parameter accumulation: negative size");
   if (nterms > 0 && (!t_param || !t_kind || !t_index || !t_coef))
     throw Error(-1, "parameter accumulation: term arrays are required");
   for (int64_t t = 0; t < nterms; ++t) {
     const int k = t_kind[t], i = t_index[t];
-    const int lim = k == 0 ? h.m : k == 1 ? h.p : k == 3 ? h.n : 1;
-    if (t_param[t] < 0 || t_param[t] >= nparam || k < 0 || k > 3 || (k != 2 && (i < 0 || i >= lim)))
+    const bool var = pv && (k == 4 || k == 5);
+    if (var && !t_var)
+      throw Error(-1, "parameter accumulation: term " + std::to_string(t) + " of kind " + std::to_string(k) +
+                          " needs t_var");
+    const int lim = k == 0 || k == 4 ? h.m : k == 1 || k == 5 ? h.p : k == 3 ? h.n : 1;
+    if (t_param[t] < 0 || t_param[t] >= nparam || k < 0 || k > (pv ? 5 : 3) || (k != 2 && (i < 0 || i >= lim)) ||
+        (var && (t_var[t] < 0 || t_var[t] >= h.n)))
       throw Error(-1, "parameter accumulation: term " + std::to_string(t) + " out of range");
   }
 }
@@ -194,7 +378,7 @@ void validate_conic(const Handle& h, int nparam, int64_t nterms, const int32_t* 
 
 // stable CSR by `key` (terms keep their relative order within a row)
 Csr csr_by(int rows, int64_t nterms, const std::vector<int32_t>& key, const int32_t* t_param,
-           const int32_t* t_kind, const int32_t* t_index, const double* t_coef) {
+           const int32_t* t_kind, const int32_t* t_index, const double* t_coef, const int32_t* t_var = nullptr) {
   Csr c;
   c.ptr.assign(rows + 1, 0);
   for (int64_t t = 0; t < nterms; ++t) ++c.ptr[key[t] + 1];
@@ -204,8 +388,10 @@ Csr csr_by(int rows, int64_t nterms, const std::vector<int32_t>& key, const int3
   c.index.resize(nterms);
   c.param.resize(nterms);
   c.coef.resize(nterms);
+  if (t_var) c.var.resize(nterms);
   for (int64_t t = 0; t < nterms; ++t) {
     const int64_t d = pos[key[t]]++;
+    if (t_var) c.var[d] = t_var[t];
     c.kind[d] = t_kind[t];
     c.index[d] = t_index[t];
     c.param[d] = t_param[t];
@@ -219,24 +405,34 @@ Csr csr_by(int rows, int64_t nterms, const std::vector<int32_t>& key, const int3
 // before `c` goes out of scope.
 struct DevCsr {
   int64_t* ptr = nullptr;
-  int32_t *kind = nullptr, *index = nullptr, *param = nullptr;
+  int32_t *kind = nullptr, *index = nullptr, *param = nullptr, *var = nullptr;
   double* coef = nullptr;
+  DevCsr() = default;
   DevCsr(Handle& h, const Csr& c) {
+    h.pterms.ensure(bytes(c));
+    place(h, c, h.pterms.as<char>());
+  }
+  static size_t bytes(const Csr& c) {
+    const size_t nt = c.coef.size(), np = c.ptr.size();
+    return (np * 8 + nt * 8 + 4 * nt * 4 + 64 + 63) / 64 * 64;
+  }
+  // the arrays at `p` (inside h.pterms, bytes(c) long), copies queued on the handle's stream
+  void place(Handle& h, const Csr& c, char* p) {
     const hipStream_t st = h.stream;
     const size_t nt = c.coef.size(), np = c.ptr.size();
-    h.pterms.ensure(np * 8 + nt * 8 + 3 * nt * 4 + 64);
-    char* p = h.pterms.as<char>();
     ptr = reinterpret_cast<int64_t*>(p);
     coef = reinterpret_cast<double*>(p + np * 8);
     kind = reinterpret_cast<int32_t*>(p + np * 8 + nt * 8);
     index = kind + nt;
     param = index + nt;
+    var = param + nt;
     DOPT_CHECK_HIP(hipMemcpyAsync(ptr, c.ptr.data(), np * 8, hipMemcpyHostToDevice, st));
     if (nt) {
       DOPT_CHECK_HIP(hipMemcpyAsync(coef, c.coef.data(), nt * 8, hipMemcpyHostToDevice, st));
       DOPT_CHECK_HIP(hipMemcpyAsync(kind, c.kind.data(), nt * 4, hipMemcpyHostToDevice, st));
       DOPT_CHECK_HIP(hipMemcpyAsync(index, c.index.data(), nt * 4, hipMemcpyHostToDevice, st));
       DOPT_CHECK_HIP(hipMemcpyAsync(param, c.param.data(), nt * 4, hipMemcpyHostToDevice, st));
+      if (!c.var.empty()) DOPT_CHECK_HIP(hipMemcpyAsync(var, c.var.data(), nt * 4, hipMemcpyHostToDevice, st));
     }
   }
 };
@@ -357,6 +553,146 @@ int jacobian_chunk(const Handle& h, int seeds) {
 }
 
 }  // namespace
+
+// ---------------------------------------------------------------------------
+// QP parameter calls on k seeds: host side
+// ---------------------------------------------------------------------------
+namespace {
+
+// Seeds per chunk.  One seed costs, per problem, its reduced right-hand side,
+// solution and full forward copy (krhs + kx + kfull: 3·nmax doubles) and, in
+// reverse without out_rev, its outputs in the handle's scratch (n+m+p).  The
+// chunk is the largest multiple of 16 (the multi-RHS kernel's seed group and
+// the output kernel's) that keeps chunk · B · that within JAC_WS_BYTES, and at
+// least 16.  DOPT_QP_JAC_CHUNK=<k ≥ 1> overrides it (the tests' chunk edges).
+int qp_jacobian_chunk(const Handle& h, int seeds) {
+  if (const char* e = getenv("DOPT_QP_JAC_CHUNK")) {
+    const int k = atoi(e);
+    if (k >= 1) return std::min(k, seeds);
+  }
+  constexpr size_t G = 16;
+  const size_t per_seed = std::max<size_t>(h.batch, 1) * (3 * (size_t)h.nmax + h.n + h.m + h.p) * sizeof(double);
+  const size_t fit = JAC_WS_BYTES / per_seed / G * G;
+  return (int)std::min<size_t>(std::max<size_t>(fit, G), (size_t)seeds);
+}
+
+void qp_k_checks(Handle& h, const char* fn) {
+  if (!h.set) throw Error(-1, std::string(fn) + ": dopt_qp_set has not been called");
+  if (h.sparse) throw Error(-1, "multi-RHS calls need factors: not on the sparse (LSQR) route");
+}
+
+const int32_t* qp_rpos(Handle& h) { return h.kidx.as<int32_t>() + (size_t)h.batch * h.m; }
+
+}  // namespace
+
+void qp_params_forward_k(Handle& h, int k, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
+                         const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
+                         double* out) {
+  qp_k_checks(h, "dopt_qp_params_forward_k");
+  if (k < 0) throw Error(-1, "dopt_qp_params_forward_k: k must not be negative");
+  validate(h, nparam, nterms, t_param, t_kind, t_index, t_coef, t_var, true);
+  if (nparam == 0 || k == 0 || h.batch == 0) return;
+  if (!out) throw Error(-1, "dopt_qp_params_forward_k: out is required");
+  if (!h.factored) qp_factor(h);
+  const int n = h.n, m = h.m, p = h.p, nmax = h.nmax;
+  const size_t B = h.batch, L = (size_t)n + m + p, blk = B * nmax;
+  // by constraint row (kinds 0, 1, 4, 5) and by variable (kinds 3, 4, 5); kind 2 is dropped
+  std::vector<int32_t> rkey, rpar, rkind, ridx, rvar, vkey, vpar, vkind, vidx, vvar;
+  std::vector<double> rco, vco;
+  for (int64_t t = 0; t < nterms; ++t) {
+    const int kd = t_kind[t], i = t_index[t], v = kd == 4 || kd == 5 ? t_var[t] : 0;
+    if (kd == 0 || kd == 1 || kd == 4 || kd == 5) {
+      rkey.push_back(kd == 0 || kd == 4 ? i : m + i);
+      rpar.push_back(t_param[t]);
+      rkind.push_back(kd);
+      ridx.push_back(i);
+      rvar.push_back(v);
+      rco.push_back(t_coef[t]);
+    }
+    if (kd == 3 || kd == 4 || kd == 5) {
+      vkey.push_back(kd == 3 ? i : v);
+      vpar.push_back(t_param[t]);
+      vkind.push_back(kd);
+      vidx.push_back(i);
+      vvar.push_back(v);
+      vco.push_back(t_coef[t]);
+    }
+  }
+  const Csr cr = csr_by(m + p, (int64_t)rkey.size(), rkey, rpar.data(), rkind.data(), ridx.data(), rco.data(),
+                        rvar.data());
+  const Csr cv = csr_by(n, (int64_t)vkey.size(), vkey, vpar.data(), vkind.data(), vidx.data(), vco.data(),
+                        vvar.data());
+  h.pterms.ensure(DevCsr::bytes(cr) + DevCsr::bytes(cv));
+  DevCsr dr, dv;
+  dr.place(h, cr, h.pterms.as<char>());
+  dv.place(h, cv, h.pterms.as<char>() + DevCsr::bytes(cr));
+  const int chunk = qp_jacobian_chunk(h, k);
+  h.krhs.ensure((size_t)chunk * blk * sizeof(double));
+  h.kx.ensure((size_t)chunk * blk * sizeof(double));
+  h.kfull.ensure((size_t)chunk * blk * sizeof(double));
+  double* rk = h.krhs.as<double>();
+  double* xk = h.kx.as<double>();
+  double* fk = h.kfull.as<double>();
+  static const double dummy = 0.0;
+  for (int s0 = 0; s0 < k; s0 += chunk) {
+    const int kc = std::min(chunk, k - s0);
+    const int64_t cols = (int64_t)kc * (int64_t)B;
+    {
+      PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
+      hipLaunchKernelGGL(qp_poi_fwd_rhs_kernel, poi_grid(nmax, cols), dim3(PTPB), 0, h.stream,
+                         dp ? dp + (size_t)s0 * B * nparam : nullptr, s0, nparam, n, m, p, nmax, (int)B, cols, dr.ptr,
+                         dr.kind, dr.param, dr.var, dr.coef, dv.ptr, dv.kind, dv.param, dv.index, dv.coef, h.z,
+                         m ? h.lam : &dummy, p ? h.nu : &dummy, qp_rpos(h), h.meta.as<QPMeta>(), fk, rk);
+      DOPT_CHECK_HIP(hipGetLastError());
+    }
+    solve_k(h, 1, kc, rk, xk, fk, out + (size_t)s0 * B * L);
+  }
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `cr` / `cv` are done
+}
+
+void qp_params_reverse_k(Handle& h, int k, const double* dl_dz, int nparam, int64_t nterms, const int32_t* t_param,
+                         const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
+                         double* out_rev, double* out_dp) {
+  qp_k_checks(h, "dopt_qp_params_reverse_k");
+  if (k < 0) throw Error(-1, "dopt_qp_params_reverse_k: k must not be negative");
+  validate(h, nparam, nterms, t_param, t_kind, t_index, t_coef, t_var, true);
+  if (nparam == 0 || k == 0 || h.batch == 0) return;
+  if (!out_dp) throw Error(-1, "dopt_qp_params_reverse_k: out_dp is required");
+  if (!h.factored) qp_factor(h);
+  const int n = h.n, m = h.m, p = h.p, nmax = h.nmax;
+  const size_t B = h.batch, L = (size_t)n + m + p, blk = B * nmax;
+  std::vector<int32_t> var(nterms, 0);
+  for (int64_t t = 0; t < nterms; ++t)
+    if (t_kind[t] == 4 || t_kind[t] == 5) var[t] = t_var[t];
+  const Csr c = csr_by(nparam, nterms, std::vector<int32_t>(t_param, t_param + nterms), t_param, t_kind, t_index,
+                       t_coef, var.data());
+  DevCsr d(h, c);
+  const int chunk = qp_jacobian_chunk(h, k);
+  h.krhs.ensure((size_t)chunk * blk * sizeof(double));
+  h.kx.ensure((size_t)chunk * blk * sizeof(double));
+  if (!out_rev) h.qjac.ensure((size_t)chunk * B * L * sizeof(double));
+  double* rk = h.krhs.as<double>();
+  double* xk = h.kx.as<double>();
+  static const double dummy = 0.0;
+  for (int s0 = 0; s0 < k; s0 += chunk) {
+    const int kc = std::min(chunk, k - s0);
+    const int64_t cols = (int64_t)kc * (int64_t)B;
+    {
+      PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
+      hipLaunchKernelGGL(qp_poi_rev_rhs_kernel, poi_grid(nmax, cols), dim3(PTPB), 0, h.stream,
+                         dl_dz ? dl_dz + (size_t)s0 * B * n : nullptr, s0, n, nmax, (int)B, cols, rk);
+      DOPT_CHECK_HIP(hipGetLastError());
+    }
+    double* rev = out_rev ? out_rev + (size_t)s0 * B * L : h.qjac.as<double>();
+    solve_k(h, 0, kc, rk, xk, nullptr, rev);
+    PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
+    hipLaunchKernelGGL(qp_poi_reverse_k_kernel, poi_grid(nparam, cols), dim3(PTPB), 0, h.stream, rev, h.z,
+                       m ? h.lam : &dummy, p ? h.nu : &dummy, n, m, p, (int)B, cols, nparam, d.ptr, d.kind, d.index,
+                       d.var, d.coef, out_dp + (size_t)s0 * B * nparam);
+    DOPT_CHECK_HIP(hipGetLastError());
+  }
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
+}
 
 void conic_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
                           const int32_t* t_kind, const int32_t* t_index, const double* t_coef, double* db,

@@ -1039,7 +1039,7 @@ void qp_forward(Handle& h, const double* dQ, const double* dq, const double* dG,
 // multi-RHS row): seed j's inputs and outputs are standard batch blocks at
 // offset j·B·len; the blocked problems' k solves run in one launch
 // (qp_multi.hip), the other routes and the outputs per seed.
-static void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out) {
+void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out) {
   const size_t blk = (size_t)h.batch * h.nmax;
   const int B = (int)h.batch, n = h.n, m = h.m, p = h.p, nmax = h.nmax;
   {

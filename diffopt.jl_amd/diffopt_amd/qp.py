@@ -283,15 +283,24 @@ class QPBatch:
 
     # ---- parameters (ParametricOptInterface glue, reference src/parameters.jl)
     @staticmethod
-    def _terms(terms):
+    def _terms(terms, with_var=False):
         """terms: iterable of (param, kind, index, coef) — kinds 0 LessThan row,
-        1 EqualTo row, 2 objective, 3 objective parameter×variable (index = v)."""
+        1 EqualTo row, 2 objective, 3 objective parameter×variable (index = v) —
+        or, for the ``_k`` calls, (param, kind, row, coef, var) — kinds 4 / 5: the
+        parameter×variable term of LessThan / EqualTo row ``row`` and variable
+        ``var``.  ``with_var``: also the variables' array (None when no term
+        carries one)."""
         t = list(terms)
         par = np.ascontiguousarray([int(x[0]) for x in t], dtype=np.int32)
         kind = np.ascontiguousarray([int(x[1]) for x in t], dtype=np.int32)
         idx = np.ascontiguousarray([int(x[2]) for x in t], dtype=np.int32)
         coef = np.ascontiguousarray([float(x[3]) for x in t], dtype=np.float64)
-        return len(t), par, kind, idx, coef
+        if not with_var:
+            return len(t), par, kind, idx, coef
+        var = None
+        if any(len(x) > 4 for x in t):
+            var = np.ascontiguousarray([int(x[4]) if len(x) > 4 else 0 for x in t], dtype=np.int32)
+        return len(t), par, kind, idx, var, coef
 
     def params_reverse(self, rev, terms, nparam):
         """ReverseConstraintSet of every parameter of every problem, (B, nparam),
@@ -323,6 +332,68 @@ class QPBatch:
                                              st.ptr(dq), st.ptr(dh) if m else None, st.ptr(db) if p_ else None)
         _lib.check(rc, self.h)
         return dq, dh, db
+
+    def params_forward_k(self, dp, terms, singular_ok=False):
+        """k parameter tangents per problem, solves included
+        (dopt_qp_params_forward_k): dp (k, B, nparam) → (k, B, n+m+p), seed j's
+        block = ``forward`` on the tangents the terms define (kinds 4 / 5: dG /
+        dA entries), the right-hand sides written straight from the term table."""
+        k, B, nparam = int(dp.shape[0]), self.batch, int(dp.shape[2])
+        nt, par, kind, idx, var, coef = self._terms(terms, True)
+        st = self._stage([dp])
+        d = vector(dp, (k, B, nparam))
+        out = Staged.empty((k, B, self.L), st.mem == _lib.DOPT_MEM_DEVICE)
+        pp = Staged.ptr
+        rc = self.lib.dopt_qp_params_forward_k(self.h, k, st.ptr(d), nparam, nt, pp(par), pp(kind), pp(idx),
+                                               pp(var), pp(coef), st.ptr(out))
+        _lib.check(rc, self.h, singular_ok)
+        return out
+
+    def params_reverse_k(self, dl_dz, terms, nparam, want_rev=False, singular_ok=False):
+        """k seeds per problem through the reverse solve and the parameter
+        accumulation (dopt_qp_params_reverse_k): dl_dz (k, B, n) → out_dp
+        (k, B, nparam), or (out_dp, rev (k, B, n+m+p)) with ``want_rev``."""
+        k, B, nparam = int(dl_dz.shape[0]), self.batch, int(nparam)
+        nt, par, kind, idx, var, coef = self._terms(terms, True)
+        st = self._stage([dl_dz])
+        d = vector(dl_dz, (k, B, self.n))
+        dev = st.mem == _lib.DOPT_MEM_DEVICE
+        out = Staged.empty((k, B, nparam), dev)
+        rev = Staged.empty((k, B, self.L), dev) if want_rev else None
+        pp = Staged.ptr
+        rc = self.lib.dopt_qp_params_reverse_k(self.h, k, st.ptr(d), nparam, nt, pp(par), pp(kind), pp(idx),
+                                               pp(var), pp(coef), st.ptr(rev), st.ptr(out))
+        _lib.check(rc, self.h, singular_ok)
+        return (out, rev) if want_rev else out
+
+    def params_jacobian(self, terms, nparam, mode, device=False, singular_ok=False):
+        """The parameter Jacobian of every problem by unit seeds, one call.
+        ``mode`` 0 (or "forward"): (B, n+m+p, nparam), column j = [dz/dp_j;
+        dλ/dp_j; dν/dp_j] (dopt_qp_params_forward_k with dp = NULL); 1 (or
+        "reverse"): (B, n, nparam), row i = ReverseConstraintSet of every
+        parameter for the seed e_i (dopt_qp_params_reverse_k with dl_dz = NULL).
+        A numpy array, or with ``device`` a torch CUDA tensor written in place
+        by the kernels (on torch's current stream); a view of the seed-major
+        buffer either way."""
+        mode = {"forward": 0, "reverse": 1}.get(mode, mode)
+        if mode not in (0, 1):
+            raise ValueError("mode must be 0 (forward) or 1 (reverse)")
+        B, n, nparam = self.batch, self.n, int(nparam)
+        nt, par, kind, idx, var, coef = self._terms(terms, True)
+        K = n if mode == 1 else nparam
+        J = Staged.empty((K, B, nparam if mode == 1 else self.L), device)
+        self._stage([J] if device else [])   # the memory mode (and torch's stream) follow the output
+        pp = Staged.ptr
+        if mode == 0:
+            rc = self.lib.dopt_qp_params_forward_k(self.h, K, None, nparam, nt, pp(par), pp(kind), pp(idx), pp(var),
+                                                   pp(coef), pp(J))
+        else:
+            rc = self.lib.dopt_qp_params_reverse_k(self.h, K, None, nparam, nt, pp(par), pp(kind), pp(idx), pp(var),
+                                                   pp(coef), None, pp(J))
+        _lib.check(rc, self.h, singular_ok)
+        if device:
+            return J.permute(1, 2, 0) if mode == 0 else J.permute(1, 0, 2)
+        return J.transpose(1, 2, 0) if mode == 0 else J.transpose(1, 0, 2)
 
     def reverse_grads(self, rev, dQ=True, dG=True, dA=True):
         """Materialised reverse gradients of every problem from a reverse
@@ -622,8 +693,18 @@ class Model:
         self.input_objective = None      # (dQ, dq)
         self.input_le = {}               # row -> (coeffs, constant)
         self.input_eq = {}
+        self.param_terms, self.nparam = [], 0
+        self.input_dp = {}               # parameter -> ForwardConstraintSet direction
+        self.back_param_cache = None
 
-    def set_problem(self, Q, q, G=None, h=None, A=None, b=None):
+    def set_problem(self, Q, q, G=None, h=None, A=None, b=None, param_terms=(), nparam=0):
+        """``param_terms``: the parametric terms of the problem's ``nparam``
+        parameters (``QPBatch._terms``: 4-tuples of kinds 0-3, 5-tuples
+        (param, kind, row, coef, var) of kinds 4 / 5), every constraint written
+        as G z ≤ h / A z = b with its parametric part on the left."""
+        self.param_terms = [tuple(t) for t in param_terms]
+        self.nparam = int(nparam)
+        self.input_dp = {}
         n = np.asarray(q).shape[0]
         self.Q = np.asarray(Q, dtype=np.float64).reshape(n, n)
         self.q = np.asarray(q, dtype=np.float64)
@@ -667,11 +748,18 @@ class Model:
         tgt = self.input_le if kind == LE else self.input_eq
         tgt[int(row)] = (np.asarray(coeffs, dtype=np.float64), float(constant))
 
+    def set_forward_parameter(self, p, value):
+        """``ForwardConstraintSet`` of ``ParameterRef(p)``: the direction ``Parameter(value)``."""
+        if not 0 <= int(p) < self.nparam:
+            raise IndexError(f"parameter {p} of {self.nparam}")
+        self.input_dp[int(p)] = float(value)
+
     def empty_input_sensitivities(self):
         self.input_dx = {}
         self.input_objective = None
         self.input_le = {}
         self.input_eq = {}
+        self.input_dp = {}
 
     # ---- engine ------------------------------------------------------------
     def _ensure(self):
@@ -695,7 +783,13 @@ class Model:
         dl = np.zeros(self.n)
         for i, v in self.input_dx.items():
             dl[i] = v
-        out = np.asarray(e.reverse(dl[None]))[0]
+        if self.nparam:   # the parameters' ReverseConstraintSet beside the getters (parameters.jl:341-534)
+            dp, rev = e.params_reverse_k(dl[None, None], self.param_terms, self.nparam, want_rev=True)
+            out = np.asarray(rev)[0, 0]
+            self.back_param_cache = np.asarray(dp)[0, 0]
+        else:
+            out = np.asarray(e.reverse(dl[None]))[0]
+            self.back_param_cache = None
         n, m = self.n, self.G.shape[0]
         self.back_grad_cache = (out[:n], out[n:n + m], out[n + m:])
         self.diff_time = time.perf_counter() - t0
@@ -716,11 +810,20 @@ class Model:
         for r, (c, k) in self.input_eq.items():
             dA[r] = c
             db[r] = -k
-        out = np.asarray(e.forward(
-            None if dQ is None else np.asarray(dQ, float)[None],
-            None if dq is None else np.asarray(dq, float)[None],
-            dG[None] if m else None, dh[None] if m else None,
-            dA[None] if p else None, db[None] if p else None))[0]
+        functions = self.input_objective is not None or self.input_le or self.input_eq
+        if functions or not self.input_dp:
+            out = np.asarray(e.forward(
+                None if dQ is None else np.asarray(dQ, float)[None],
+                None if dq is None else np.asarray(dq, float)[None],
+                dG[None] if m else None, dh[None] if m else None,
+                dA[None] if p else None, db[None] if p else None))[0]
+        else:
+            out = np.zeros(n + m + p)
+        if self.input_dp:   # the parameters' tangents on top of the functions' (parameters.jl:91-300): the
+            dp = np.zeros((1, 1, self.nparam))   # solve is linear in the right-hand side, so the two solutions add
+            for par, v in self.input_dp.items():
+                dp[0, 0, par] = v
+            out = out + np.asarray(e.params_forward_k(dp, self.param_terms))[0, 0]
         self.forw_grad_cache = (out[:n], out[n:n + m], out[n + m:])
         self.diff_time = time.perf_counter() - t0
 
@@ -747,6 +850,10 @@ class Model:
         if kind == EQ:
             return dnu[row] * z + self._nu[row] * dz, dnu[row]
         raise ValueError(kind)
+
+    def reverse_parameter(self, p):
+        """``ReverseConstraintSet`` of ``ParameterRef(p)`` (parameters.jl:341-534)."""
+        return float(self.back_param_cache[p])
 
     def differentiate_time_sec(self):
         return self.diff_time

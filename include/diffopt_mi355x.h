@@ -296,6 +296,44 @@ int dopt_qp_params_reverse(dopt_handle* h, const double* rev, int32_t nparam, in
 int dopt_qp_params_forward(dopt_handle* h, const double* dp, int32_t nparam, int64_t nterms,
                            const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
                            const double* t_coef, double* dq, double* dh, double* db);
+/* The parameter calls on k seeds, solves included (the `_k` contract above:
+ * seed-major blocks, one factorisation, dense-route handles only, the return
+ * value is the first singular problem's info).  Two more term kinds, the
+ * parameter×variable terms c·p·x_v of a ParametricQuadraticFunction constraint
+ * (parameters.jl:147-203 forward, :390-441 reverse):
+ *   4  of LessThan row t_index[t] ∈ [0, m), variable t_var[t] ∈ [0, n)
+ *   5  of EqualTo row t_index[t] ∈ [0, p), variable t_var[t]
+ * t_var may be NULL when no term has kind 4 or 5 and is ignored for kinds 0-3.
+ * dopt_qp_params_forward / dopt_qp_params_reverse above keep refusing kinds 4
+ * and 5 ("out of range"): they have no dG / dA to write such a term to.
+ * Parameter×parameter terms (parameters.jl:161-178) multiply by the VALUE of
+ * the other parameter, which differs per problem while a coefficient here is
+ * shared by the batch: the caller folds them into kind 0, 1 or 2 terms per
+ * batch of equal values.
+ * dopt_qp_params_forward_k: dp nparam×B×k (k blocks in dopt_qp_params_forward's
+ * layout), out (n+m+p)×B×k as dopt_qp_forward_k's.  Seed j's block equals, to
+ * rounding, dopt_qp_forward on the tangents the terms define — dq_v = Σ c·dp
+ * (kind 3), dh_i = −Σ c·dp (kind 0), db_i = −Σ c·dp (kind 1), dG[i,v] = Σ c·dp
+ * (kind 4), dA[i,v] = Σ c·dp (kind 5), kind 2 dropped — but the right-hand
+ * sides are written straight from the term table: no dense tangent is formed.
+ * dp == NULL: unit seeds, k must equal nparam (else −1), seed j is e_j — the
+ * forward-mode Jacobian: block j = [dz/dp_j; dλ/dp_j; dν/dp_j].
+ * dopt_qp_params_reverse_k: dl_dz n×B×k as dopt_qp_reverse_k's, out_rev
+ * (n+m+p)×B×k (may be NULL), out_dp nparam×B×k = Σ_t c_t·s_t with s the getter
+ * the reference reads: kinds 0-3 as dopt_qp_params_reverse, kind 4
+ * λ_i·dλ_i·z_v + λ_i·dz_v, kind 5 dν_i·z_v + ν_i·dz_v (the dG / dA entries of
+ * dopt_qp_reverse_grads).  dl_dz == NULL: unit seeds, k must equal n, seed i is
+ * e_i — the reverse-mode Jacobian: block i is row i of dz/dp.
+ * nparam == 0, k == 0 or batch == 0: nothing is written, 0 is returned; k < 0
+ * returns −1.  A seed's block does not depend on how the seeds are grouped
+ * (chunks of a multiple of 16 seeds within 1 GiB of work vectors; the
+ * environment variable DOPT_QP_JAC_CHUNK=<k ≥ 1> overrides the chunk). */
+int dopt_qp_params_forward_k(dopt_handle* h, int32_t k, const double* dp, int32_t nparam, int64_t nterms,
+                             const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                             const int32_t* t_var, const double* t_coef, double* out);
+int dopt_qp_params_reverse_k(dopt_handle* h, int32_t k, const double* dl_dz, int32_t nparam, int64_t nterms,
+                             const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
+                             const int32_t* t_var, const double* t_coef, double* out_rev, double* out_dp);
 
 /* ---- ConicProgram ----------------------------------------------------------
  * A: m×n MOI coefficients (A_moi x + b ∈ K; the diffcp sign flip of
