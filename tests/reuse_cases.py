@@ -8,7 +8,9 @@ sizes (the padded batch size, the multi-RHS buffers), factorisation kinds
 (no-pivot / partial pivoting / generic / LSQR / the one-workgroup small
 path), the P-symmetric route, staging and memory mode, the sparse route, and
 for conic handles the cone table, the packed Dπ length and the large-PSD
-scratch.
+scratch; for NLP handles the structure (num_w, the bound blocks, the rows of
+M), the route of single problems (reduced, inertia-corrected on the full M,
+asymmetric), the speculative launch's switch and a deferred factorisation.
 
 A step is a dict: ``name``, ``data`` (the generator's arrays, batch-stacked;
 never modified by a test), and the properties it is built to have —
@@ -21,7 +23,11 @@ never modified by a test), and the properties it is built to have —
   setter: "set", "csc" or "device");
 * conic: ``cones`` and ``comparable`` (the oracle's LSQR converges, istop
   1–2, forward and reverse, on every problem: the step is held to the oracle
-  at 1e-6 with no relaxed output).
+  at 1e-6 with no relaxed output);
+* NLP: ``st`` (the structure), ``restructure`` (the step calls set_structure
+  first), ``nsys`` (n + c on the reduced route, the rows of M for a corrected
+  problem), ``corrected`` and ``asym`` (the problems concerned), ``saddle``
+  (equalities only, no bounds: M itself is the saddle-point matrix).
 
 Sequences are built once per process (lru_cache) and shared."""
 
@@ -29,8 +35,9 @@ import functools
 
 import numpy as np
 
-from diffopt_amd.synthetic import conic_numpy, conic_numpy_wellcond, lp_sparse_numpy, qp_numpy
+from diffopt_amd.synthetic import conic_numpy, conic_numpy_wellcond, lp_sparse_numpy, nlp_numpy, qp_numpy
 from oracle import conic as ocn
+from oracle import nlp as onlp
 from oracle import qp as oqp
 
 LSQR, NOPIV, PIVOT, SMALL = 0, 1, 2, 3   # _lib.LU_KIND_*
@@ -329,3 +336,75 @@ def conic_oracle(step, b):
         _CONIC_REF[key] = dict(fwd=np.concatenate([du, dv, [dw]]), dx=odx, g=og, dA=odA, db=odb, dc=odc,
                                info=(fi, ri), cache=cache, data=d)   # (d held: its id stays unique)
     return _CONIC_REF[key]
+
+
+# ---------------------------------------------------------------------------
+# NLP
+# ---------------------------------------------------------------------------
+NLP_SHAPE = (4, 20, 12, 4)
+NLP_KEYS = ("Hxx", "Hxp", "Jx", "Jp", "x", "cval", "crhs", "y", "xl", "xu", "yl", "yu")
+
+
+def _nlp_points(seed, count, **kw):
+    """`count` batches of one structure: nlp_numpy draws the structure first,
+    then problem after problem, so one draw of count·B problems is cut up."""
+    B, n, c, P = NLP_SHAPE
+    st, pt, dp, dx, dd = nlp_numpy(count * B, n, c, P, seed, **kw)
+    cut = lambda a, i: a[i * B:(i + 1) * B].copy()
+    return st, [dict(pt={k: cut(v, i) for k, v in pt.items()}, dp=cut(dp, i), dx=cut(dx, i), dd=cut(dd, i))
+                for i in range(count)]
+
+
+def _nlp_step(name, st, d, restructure, corrected=(), asym=()):
+    B, n, c, P = NLP_SHAPE
+    L = onlp.Layout(st["con_kind"], st["has_low"], st["has_up"])
+    return dict(name=name, st=st, data=d, restructure=restructure, corrected=list(corrected), asym=list(asym),
+                nsys=[L.rows if b in corrected else n + c for b in range(B)], saddle=L.rows == n + c)
+
+
+@functools.lru_cache(maxsize=None)
+def nlp_structures():
+    """k. one NLP handle: a generic structure (bounds, all three row kinds);
+    equalities only without bounds (num_w and the rows shrink to n + c, the
+    saddle-only route); all inequalities (num_w grows); the first structure
+    with problem 1 singular (two identical equality rows: inertia-corrected,
+    on the full M); the same structure with a regular point (no shift or
+    correction may survive, every problem reduced again); problem 2 with an
+    asymmetric Hxx (the speculative launch misses and is switched off); the
+    first structure set again with the first point (the launch is tried
+    again), whose outputs equal the first step's bit for bit."""
+    # (seed 8806: the oracle's SuperLU cancels the dependent pivot to exactly
+    # zero and corrects, as the reference's UMFPACK does — on other draws it is
+    # left at rounding level, test_nlp_gpu.test_saddle_only_dependent_equality;
+    # test_reuse_cases_cpu.py holds the step to it)
+    first, (a, sing, regular, asym) = _nlp_points(8806, 4)
+    eq, (e0,) = _nlp_points(8801, 1, frac_geq=0, frac_leq=0, frac_low=0, frac_up=0)
+    ineq, (i0,) = _nlp_points(8802, 1, frac_geq=0.5, frac_leq=0.5)
+    i, j = np.flatnonzero(first["con_kind"] == 0)[:2]
+    sing["pt"]["Jx"][1, j] = sing["pt"]["Jx"][1, i]
+    sing["pt"]["Jp"][1, j] = sing["pt"]["Jp"][1, i]
+    n = NLP_SHAPE[1]
+    asym["pt"]["Hxx"][2] = asym["pt"]["Hxx"][2] + 0.05 * np.triu(np.random.default_rng(3).standard_normal((n, n)), 1)
+    return [
+        _nlp_step("generic structure", first, a, True),
+        _nlp_step("equalities only, no bounds", eq, e0, True),
+        _nlp_step("all inequalities", ineq, i0, True),
+        _nlp_step("first structure, problem 1 singular", first, sing, True, corrected=[1]),
+        _nlp_step("regular point", first, regular, False),
+        _nlp_step("problem 2 asymmetric", first, asym, False, asym=[2]),
+        _nlp_step("first structure and point again", first, a, True),
+    ]
+
+
+_NLP_REF = {}
+
+
+def nlp_oracle(step, b):
+    """(∂s, Layout, corrections) of problem b, computed once per step."""
+    key = (id(step["data"]), b)
+    if key not in _NLP_REF:
+        st, pt = step["st"], step["data"]["pt"]
+        ds, L, _, _, corr = onlp.compute_sensitivity(st["con_kind"], st["has_low"], st["has_up"], st["sense"],
+                                                     *[pt[k][b] for k in NLP_KEYS], return_info=True)
+        _NLP_REF[key] = (ds, L, corr, step["data"])   # (data held: its id stays unique)
+    return _NLP_REF[key][:3]

@@ -1,5 +1,5 @@
 """One long-lived handle, model after model (the Julia QPModel / ConicModel's
-pattern, bench.py's, the sharded driver's): after every `set` of every
+pattern, an NLP model re-solved with a new active set, bench.py's, the sharded driver's): after every `set` of every
 sequence of reuse_cases.py the handle must behave exactly as a fresh handle of
 the same shape and environment given the same model —
 
@@ -50,6 +50,12 @@ def QPBatch():
 def ConicBatch():
     from diffopt_amd.conic import ConicBatch
     return ConicBatch
+
+
+@pytest.fixture(scope="module")
+def NLPBatch():
+    from diffopt_amd.nlp import NLPBatch
+    return NLPBatch
 
 
 @pytest.fixture(params=["nopiv", "pivot"])
@@ -548,6 +554,93 @@ def test_conic_failed_set_leaves_no_model(ConicBatch, conic_route):
     nothing_set()
     _same(good(), first, "good set after a bad cone table")
     e.close()
+
+
+# ---------------------------------------------------------------------------
+# NLP
+# ---------------------------------------------------------------------------
+def _nlp_set(e, st):
+    if st["restructure"]:
+        s = st["st"]
+        e.set_structure(s["con_kind"], s["has_low"], s["has_up"], s["sense"])
+    e.set(*[st["data"]["pt"][k] for k in rc.NLP_KEYS])
+
+
+def _nlp_getters(e, tag, out):
+    out[tag + ".corrections"] = e.corrections()
+    out[tag + ".system_size"] = e.system_size()
+    out[tag + ".lu_kind"] = e.lu_kind()
+
+
+def _nlp_calls(e, st):
+    """forward_reverse on the unfactorised point; then factor + one call, four
+    times (in the deferred form each call finishes its own pending
+    factorisation); the getters straight after a factor()."""
+    d = st["data"]
+    out = {}
+    out["fr.dx"], out["fr.dd"], out["fr.dp"] = e.forward_reverse(d["dp"], d["dx"], d["dd"])
+    _nlp_getters(e, "fr", out)
+    e.factor()
+    _nlp_getters(e, "factor", out)
+    e.factor()
+    out["fwd.dx"], out["fwd.dd"] = e.forward(d["dp"])
+    e.factor()
+    out["rev.dp"] = e.reverse(d["dx"], d["dd"])
+    e.factor()
+    out["jac"] = e.jacobian()
+    _nlp_getters(e, "last", out)
+    out["rows"] = np.asarray(e.layout()["rows"])
+    return out
+
+
+def _nlp_oracle_check(st, out):
+    from oracle import nlp as onlp
+    d = st["data"]
+    for b in range(rc.NLP_SHAPE[0]):
+        ds, L, corr = rc.nlp_oracle(st, b)
+        assert out["last.corrections"][b] == corr, (st["name"], b)
+        ox, od = onlp.forward(ds, L, d["dp"][b])
+        op = onlp.reverse(ds, L, d["dx"][b], d["dd"][b])
+        for tag in ("fr", "fwd"):
+            got = np.concatenate([out[tag + ".dx"][b], out[tag + ".dd"][b]])
+            assert relfro(got, np.concatenate([ox, od])) <= RTOL, (st["name"], b, tag)
+        for key in ("fr.dp", "rev.dp"):
+            assert relfro(out[key][b], op) <= RTOL, (st["name"], b, key)
+        assert relfro(out["jac"][b], ds) <= RTOL, (st["name"], b, "jac")
+
+
+@pytest.mark.parametrize("deferred", [False, True], ids=["sync", "deferred"])
+def test_nlp_structure_and_route_transitions(NLPBatch, default_env, deferred):
+    """k. one NLP handle through reuse_cases.nlp_structures: dopt_nlp_set_structure
+    changing num_w / nlo / nup and the rows of M on the live handle, a
+    corrected problem (shift, corrections, the full M) followed by a regular
+    point, an asymmetric problem (the speculative launch off) followed by a
+    new structure.  In the deferred form every step also leaves a
+    factorisation pending, which the next step's set drops
+    (nlp_drop_pending)."""
+    steps = rc.nlp_structures()
+    B, n, c, P = rc.NLP_SHAPE
+    e = NLPBatch(B, n, c, P, deferred=deferred)
+    outs = []
+    for i, st in enumerate(steps):
+        _nlp_set(e, st)
+        out = _nlp_calls(e, st)
+        if deferred:
+            e.factor()   # left pending
+        f = NLPBatch(B, n, c, P, deferred=deferred)
+        _nlp_set(f, dict(st, restructure=True))
+        want = _nlp_calls(f, st)
+        f.close()
+        where = f"step {i} ({st['name']})"
+        _same(out, want, where)
+        for tag in ("fr", "factor", "last"):
+            np.testing.assert_array_equal(out[tag + ".system_size"], st["nsys"], err_msg=where)
+            np.testing.assert_array_equal(out[tag + ".corrections"] != 0, [b in st["corrected"] for b in range(B)],
+                                          err_msg=where)
+        _nlp_oracle_check(st, out)
+        outs.append(out)
+    e.close()
+    _same(outs[-1], outs[0], "the first structure and point again")
 
 
 def _raw_conic_set_csc(e, mats, b, c, x, s, y):

@@ -27,117 +27,8 @@ import numpy as np
 import pytest
 
 from diffopt_amd.synthetic import nlp_numpy
+from nlp_edge_cases import bounds as _bounds, reduced_solve   # the numpy elimination (shared with the edge cases)
 from oracle import nlp
-
-
-def _bounds(L, X, V_L, X_L, V_U, X_U):
-    w, c = L.num_w, L.c
-    lo0, up0 = w + c, w + c + L.nlo
-    out = []   # (row of M, w index j, V, coefficient of ν in row j, d)
-    for i, j in enumerate(L.has_low):
-        out.append((lo0 + i, j, V_L[j], -1.0, X[j] - X_L[j]))
-    for i, j in enumerate(L.has_up):
-        out.append((up0 + i, j, V_U[j], 1.0, X_U[j] - X[j]))
-    return out
-
-
-def reduced_solve(L, Hxx, Jx, bounds, r, trans):
-    """z = M⁻¹ r (trans False) or M⁻ᵀ r (trans True) through R.  Returns None
-    when the problem takes the full route."""
-    n, c, w = L.n, L.c, L.num_w
-    H = Hxx.T if trans else Hxx
-    rr = np.array(r, dtype=float)
-    delta = np.zeros(w)
-    known = {}
-    act = {}
-    for row, j, V, cf, d in bounds:
-        a, b = (cf, V) if trans else (V, cf)
-        if d != 0.0:
-            delta[j] += -a * b / d
-            rr[j] -= b * r[row] / d
-    for row, j, V, cf, d in bounds:
-        a, b = (cf, V) if trans else (V, cf)
-        if d == 0.0:
-            if a == 0.0 or j in known:
-                return None
-            known[j] = r[row] / a
-            act[j] = (row, b)
-    slack_of = {}
-    for t, k in enumerate(list(L.geq) + list(L.leq)):
-        slack_of[k] = n + t
-    # constraint-row states: 0 kept (equality or active slack), 1 y known,
-    # 2 regularized; rhs of the reduced rows
-    N = n + c
-    Rm = np.zeros((N, N))
-    rhs = np.zeros(N)
-    xknown = {j: v for j, v in known.items() if j < n}
-    ystate = np.zeros(c, dtype=int)
-    yval = np.zeros(c)
-    rho = np.zeros(c)
-    for k in range(c):
-        rhs[n + k] = r[w + k]
-        if k in slack_of:
-            t = slack_of[k]
-            if t in known:
-                rhs[n + k] += known[t]
-            elif delta[t] == 0.0:
-                ystate[k], yval[k] = 1, -rr[t]
-            else:
-                ystate[k], rho[k] = 2, 1.0 / delta[t]
-                rhs[n + k] += rr[t] / delta[t]
-    for j in range(n):
-        rhs[j] = rr[j]
-    # reduced matrix, identity rows / columns for the known unknowns
-    for j in range(n):
-        for jj in range(n):
-            Rm[j, jj] = H[j, jj] + (delta[j] if j == jj else 0.0)
-        for k in range(c):
-            Rm[j, n + k] = Jx[k, j]
-            Rm[n + k, j] = Jx[k, j]
-    for k in range(c):
-        Rm[n + k, n + k] = -rho[k] if ystate[k] == 2 else 0.0
-    for j, v in xknown.items():
-        rhs[:n] -= Rm[:n, j] * v
-        rhs[n:] -= Rm[n:, j] * v
-    for k in range(c):
-        if ystate[k] == 1:
-            rhs[:n] -= Rm[:n, n + k] * yval[k]
-    for j, v in xknown.items():
-        Rm[j, :] = 0.0
-        Rm[:, j] = 0.0
-        Rm[j, j] = 1.0
-        rhs[j] = v
-    for k in range(c):
-        if ystate[k] == 1:
-            Rm[n + k, :] = 0.0
-            Rm[:, n + k] = 0.0
-            Rm[n + k, n + k] = 1.0
-            rhs[n + k] = yval[k]
-    sol = np.linalg.solve(Rm, rhs)
-    x, y = sol[:n], sol[n:]
-    z = np.zeros(len(r))
-    z[:n] = x
-    z[w:w + c] = y
-    for k in range(c):
-        if k in slack_of:
-            t = slack_of[k]
-            if t in known:
-                z[t] = known[t]
-            elif ystate[k] == 1:
-                z[t] = Jx[k] @ x - r[w + k]
-            else:
-                z[t] = (rr[t] + y[k]) / delta[t]
-    for row, j, V, cf, d in bounds:
-        a, b = (cf, V) if trans else (V, cf)
-        if d != 0.0:
-            z[row] = (r[row] - a * z[j]) / d
-    for j, (row, b) in act.items():
-        if j < n:   # row j of the system: (H x)_j + δ_j x_j + (Jᵀ y)_j + b ν = r̃_j
-            z[row] = (rr[j] - H[j] @ x - delta[j] * x[j] - Jx[:, j] @ y) / b
-        else:       # slack row: −y_k + b ν = r̃_t
-            k = [kk for kk, t in slack_of.items() if t == j][0]
-            z[row] = (rr[j] + y[k]) / b
-    return z
 
 
 @pytest.mark.parametrize("sense", [1, -1])

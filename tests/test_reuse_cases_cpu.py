@@ -3,7 +3,8 @@ steps state — on the oracle alone, no GPU: the reduced size N' of every
 problem (the reference's exact elimination set), the `iterative` branch, the
 sizes' place relative to the engine's route thresholds, and for the conic
 steps flagged oracle-comparable that the oracle's LSQR converges (istop 1–2)
-in both directions on every problem.  A generator change that lets a sequence
+in both directions on every problem, and for the NLP steps the structure's
+sizes, the oracle's corrections and the problems' symmetry.  A generator change that lets a sequence
 degenerate (a step no longer growing, a model no longer converging) fails
 here, not silently in test_handle_reuse_gpu.py."""
 
@@ -110,3 +111,29 @@ def test_conic_sequences_change_what_they_claim():
     assert all(sum(d for _, d in st["cones"]) == rc.BIG_PSD_M for st in big)
     assert big[0]["cones"][0] == (4, 66 * 67 // 2) and all(c != 4 for c, _ in big[1]["cones"])
     assert big[2]["data"] is big[0]["data"]
+
+
+def test_nlp_steps_have_their_stated_properties():
+    from oracle import nlp as onlp
+    steps = rc.nlp_structures()
+    B, n, c, P = rc.NLP_SHAPE
+    lay = [onlp.Layout(s["st"]["con_kind"], s["st"]["has_low"], s["st"]["has_up"]) for s in steps]
+    # num_w / nlo / nup change on the live handle: shrink to the saddle-only shape, grow past the first
+    assert lay[1].num_w == n and lay[1].nlo == lay[1].nup == 0 and lay[1].rows == n + c and steps[1]["saddle"]
+    assert lay[2].num_w == n + c > lay[0].num_w > n and lay[2].rows > lay[0].rows > n + c
+    assert (steps[2]["st"]["con_kind"] != 0).all() and lay[0].nlo > 0 and lay[0].nup > 0
+    assert [s["restructure"] for s in steps] == [True, True, True, True, False, False, True]
+    assert all(s["st"] is steps[0]["st"] for s in steps[3:]) and steps[6]["data"] is steps[0]["data"]
+    assert [s["corrected"] for s in steps] == [[], [], [], [1], [], [], []]
+    assert [s["asym"] for s in steps] == [[], [], [], [], [], [2], []]
+    for s, L in zip(steps, lay):
+        pt = s["data"]["pt"]
+        assert pt["x"].shape == (B, n) and pt["Jx"].shape == (B, c, n) and pt["Hxp"].shape == (B, n, P)
+        assert s["data"]["dd"].shape == (B, c + len(L.low_p) + len(L.up_p))
+        for b in range(B):
+            _, _, corr = rc.nlp_oracle(s, b)
+            assert (corr >= 1) == (b in s["corrected"]) and corr >= 0, (s["name"], b, corr)
+            assert s["nsys"][b] == (L.rows if b in s["corrected"] else n + c)
+            assert np.array_equal(pt["Hxx"][b], pt["Hxx"][b].T) == (b not in s["asym"]), (s["name"], b)
+    # the regular point after the corrected one is another point of the same structure
+    assert not np.array_equal(steps[4]["data"]["pt"]["Jx"], steps[3]["data"]["pt"]["Jx"])
