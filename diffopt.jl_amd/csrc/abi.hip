@@ -195,6 +195,7 @@ int dopt_create(dopt_handle** out, int device, int64_t batch, int32_t n, int32_t
     if (const char* e = getenv("DOPT_LU")) h->lu_mode = atoi(e) != 0;
     if (const char* e = getenv("DOPT_SYM")) h->sym_mode = atoi(e) != 0;
     if (const char* e = getenv("DOPT_LEFT")) h->left_mode = atoi(e) != 0;
+    if (const char* e = getenv("DOPT_QP_SUMMARY")) h->summary_mode = atoi(e) != 0;
     if (const char* e = getenv("DOPT_NLP_REDUCE")) h->nlp_reduce = atoi(e) != 0;
     if (const char* e = getenv("DOPT_SPLIT_FUSE")) h->split_fuse = atoi(e) != 0;
     if (kind == DOPT_KIND_QP) {
@@ -256,6 +257,7 @@ int dopt_destroy(dopt_handle* h) {
   }
   for (auto e : h->ev_pool) (void)hipEventDestroy(e);
   if (h->meta_host) (void)hipHostFree(h->meta_host);
+  if (h->qsum) (void)hipHostFree(h->qsum);
   if (h->pin_ev) (void)hipEventDestroy(h->pin_ev);
   if (h->meta_ev) (void)hipEventDestroy(h->meta_ev);
   if (h->meta_fork) (void)hipEventDestroy(h->meta_fork);

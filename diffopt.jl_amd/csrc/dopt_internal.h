@@ -104,6 +104,18 @@ struct QPMeta {
                      // the meta above is a placeholder of the reduced size and the factorisation is redone
 };
 
+// What the host needs of a whole batch's metadata before it sizes the
+// factorisation, written by the prepare kernel's last workgroup into pinned
+// host memory (qp_assemble.hip); `done` holds the call's epoch once the four
+// values above it are in place.
+struct QPSummary {
+  int32_t blocked_npmax;    // largest padded size of a ROUTE_BLOCKED problem (0: none)
+  int32_t has_generic;      // some problem takes ROUTE_GENERIC
+  int32_t has_lsqr;         // some problem takes ROUTE_LSQR
+  int32_t nonsym_blocked;   // ROUTE_BLOCKED problems with sym == 0
+  uint32_t done;            // the epoch of the prepare launch that wrote the block
+};
+
 constexpr int ASM_WPP = 16;          // assembly tile workgroups per problem (qp_assemble.hip)
 constexpr int SM_MAX = 128;          // small-problem path (qp_small.hip): largest reduced system held in LDS
 constexpr int SM_BATCH = 8;          // ... and the largest batch it takes (one model at a time: the Julia back-end)
@@ -244,6 +256,15 @@ struct Handle {
   QPMeta* meta_host = nullptr;     // pinned copy of `meta` (asynchronous read-back)
   hipEvent_t meta_ev = nullptr;    // recorded after the read-back copy
   hipEvent_t meta_fork = nullptr;  // the LU's end on the handle's stream (the read-back on `aux` waits for it)
+  // the prepare kernel's summary of a whole batch's metadata (QPSummary, pinned
+  // and coherent: the host polls it instead of copying `meta` back); env
+  // DOPT_QP_SUMMARY=0: the copy of every QPMeta and the host's loops over it
+  int32_t summary_mode = 1;
+  QPSummary* qsum = nullptr;
+  DevBuf qarrive;                  // the prepare workgroups' arrival counter (0 between launches) and their
+                                   // per-problem words (nsys, iterative, sym) the last one reduces
+  uint32_t qsum_epoch = 0;         // epoch of the last summarising prepare launch (never 0)
+  int32_t nonsym_blocked = 0;      // blocked problems of the current factorisation that are not P-symmetric
   // factorisation: 1 = no-pivot blocked LU with the threshold test and a
   // partial-pivoting re-factorisation of rejected problems (default);
   // 0 = partial pivoting for every problem (env DOPT_LU=0)

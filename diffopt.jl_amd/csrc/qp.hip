@@ -15,6 +15,9 @@
 //   s     : m doubles  (G z − h, Julia sparse-matvec summation order)
 //   kidx  : m int32 (kept inequality rows, ascending)  rpos: m int32 (row → kk | -1)
 //   meta  : QPMeta {nk, nsys, iterative, info, lu}
+#include <chrono>
+#include <cstring>
+
 #include "device_prims.h"
 #include "lsqr_core.h"
 #include "qp_assemble.h"
@@ -675,14 +678,16 @@ static QPIn qp_inputs(Handle& h) {
 
 static int32_t* rpos_of(Handle& h) { return h.kidx.as<int32_t>() + (size_t)h.batch * h.m; }
 
-// prepare (s, kept rows, metadata) + assembly of `count` problems (plist:
-// their indices; null = all).  `after_prep` runs between the two launches
-// (the metadata read-back: it only needs the prepare kernel, so the host's
-// wait overlaps the tile kernel).  `full`: every tile, also for P-symmetric
-// problems (the partial-pivoting paths read the whole K).
-template <class F>
-static void prep_assemble(Handle& h, const int32_t* plist, int count, bool full, F&& after_prep) {
-  if (count == 0) return;
+// Whether a whole-batch prepare summarises its metadata for the host
+// (QPSummary).  The no-pivot route only: partial pivoting for all (lu_mode 0)
+// reads every problem's size on the host.
+static bool use_summary(const Handle& h) { return h.summary_mode && h.lu_mode == 1 && h.batch > 0; }
+
+// prepare (s, kept rows, metadata) of `count` problems (plist: their indices;
+// null = all).  `full`: no P-symmetric route (the partial-pivoting paths read
+// the whole K), so no Q symmetry check.  `summary` (whole batch only): the
+// kernel's last workgroup writes the batch's QPSummary under a new epoch.
+static void prepare(Handle& h, const int32_t* plist, int count, bool full, bool summary) {
   const QPIn P = qp_inputs(h);
   if (!full && h.n > 0) {
     // Q's symmetry check (P-symmetric route) beside the prepare kernel, on the
@@ -699,24 +704,49 @@ static void prep_assemble(Handle& h, const int32_t* plist, int count, bool full,
     DOPT_CHECK_HIP(hipEventRecord(h.ev_qsym, h.aux));
     h.qsym_pending = true;
   }
+  QPSummary* sum = nullptr;
+  unsigned* arrive = nullptr;
+  if (summary) {
+    if (!h.qsum) {
+      DOPT_CHECK_HIP(hipHostMalloc((void**)&h.qsum, sizeof(QPSummary), hipHostMallocCoherent));
+      std::memset(h.qsum, 0, sizeof(QPSummary));
+      // the arrival counter (16 bytes; the last arriver of a launch puts 0 back), then one word per problem
+      h.qarrive.ensure(16 + (size_t)h.batch * sizeof(unsigned long long));
+      DOPT_CHECK_HIP(hipMemsetAsync(h.qarrive.p, 0, 16, h.stream));
+    }
+    if (++h.qsum_epoch == 0) h.qsum_epoch = 1;   // never 0: the block starts zeroed
+    sum = h.qsum;
+    arrive = h.qarrive.as<unsigned>();
+  }
   const dim3 pg(count), pb(prep_threads(h.m));
   if (prep_rows_per_thread(h.m) == 2)
     hipLaunchKernelGGL(qp_prep_kernel<2>, pg, pb, prep_lds(h.n), h.stream, P, h.s.as<double>(),
                        h.kidx.as<int32_t>(), rpos_of(h), h.kls.as<double>(), h.gk.as<double>(), h.batch, h.meta.as<QPMeta>(),
-                       plist, h.kamax.as<double>(), h.sym_mode);
+                       plist, h.kamax.as<double>(), h.sym_mode, sum, arrive, h.qsum_epoch);
   else
     hipLaunchKernelGGL(qp_prep_kernel<1>, pg, pb, prep_lds(h.n), h.stream, P, h.s.as<double>(),
                        h.kidx.as<int32_t>(), rpos_of(h), h.kls.as<double>(), h.gk.as<double>(), h.batch, h.meta.as<QPMeta>(),
-                       plist, h.kamax.as<double>(), h.sym_mode);
+                       plist, h.kamax.as<double>(), h.sym_mode, sum, arrive, h.qsum_epoch);
   check_launch();
-  after_prep();
+}
+
+// The reduced-KKT tiles of those problems (after their prepare).  `full`:
+// every tile, also for P-symmetric problems.
+static void assemble_tiles(Handle& h, const int32_t* plist, int count, bool full) {
+  const QPIn P = qp_inputs(h);
   hipLaunchKernelGGL(qp_asm_tile_kernel, dim3((unsigned)count * ASM_WPP), dim3(512), 0, h.stream, P,
                      h.kidx.as<int32_t>(), h.kls.as<double>(), h.gk.as<double>(), h.batch, h.meta.as<QPMeta>(),
                      h.K.as<double>(), h.ld,
                      h.nmax, plist, full ? 1 : 0, h.kamax.as<double>());
   check_launch();
 }
-static void prep_assemble(Handle& h, const int32_t* plist, int count) { prep_assemble(h, plist, count, true, [] {}); }
+
+// Re-assembly of the problems in plist, every tile.
+static void prep_assemble(Handle& h, const int32_t* plist, int count) {
+  if (count == 0) return;
+  prepare(h, plist, count, true, false);
+  assemble_tiles(h, plist, count, true);
+}
 
 // Asynchronous read-back of the per-problem metadata into pinned memory; the
 // caller may queue independent kernels before waiting (meta_wait), so the
@@ -748,20 +778,83 @@ static void meta_copy_side(Handle& h) {
   DOPT_CHECK_HIP(hipEventRecord(h.meta_ev, h.crit));
 }
 
-// After the assembly: largest padded blocked system (sizes the blocked
-// launches), whether any problem needs the generic or the LSQR kernels.
-static void meta_sizes(Handle& h) {
+// The host's wait for the prepare kernel's summary of this call (epoch
+// h.qsum_epoch): a poll of the pinned block's `done` word, bounded by wall
+// clock; past the bound the stream is drained, after which the block is
+// written.  No event and no copy stand between the prepare kernel and the
+// kernels queued behind it.
+constexpr auto SUMMARY_POLL_BOUND = std::chrono::milliseconds(50);
+static void summary_wait(Handle& h) {
+  const uint32_t epoch = h.qsum_epoch;
+  const auto t0 = std::chrono::steady_clock::now();
+  for (unsigned spin = 1;; ++spin) {
+    if (__atomic_load_n(&h.qsum->done, __ATOMIC_ACQUIRE) == epoch) return;
+    if ((spin & 1023) == 0 && std::chrono::steady_clock::now() - t0 > SUMMARY_POLL_BOUND) break;
+  }
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
+  if (__atomic_load_n(&h.qsum->done, __ATOMIC_ACQUIRE) != epoch)
+    throw Error(-1, "QP prepare: the batch summary was not written");
+}
+
+// After the prepare kernel: largest padded blocked system (sizes the blocked
+// launches), whether any problem needs the generic or the LSQR kernels, how
+// many blocked problems are not P-symmetric — from the kernel's summary
+// (`summarised`: prepare ran with one; the assembly tiles are then queued
+// here, and only if some problem is assembled at all), else from the copy of
+// every QPMeta.  A batch with generic problems takes the copy as well: the
+// host lists them per problem (factor_blocked).
+static void meta_sizes(Handle& h, bool summarised) {
+  if (summarised) {
+    summary_wait(h);
+    const QPSummary& sm = *h.qsum;
+    if (!sm.has_generic) {
+      h.blocked_npmax = sm.blocked_npmax;
+      h.has_generic = false;
+      h.has_lsqr = sm.has_lsqr != 0;
+      h.nonsym_blocked = sm.nonsym_blocked;
+      if (sm.nonsym_blocked || sm.has_lsqr) {   // else every problem is P-symmetric: no tile is written
+        PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
+        assemble_tiles(h, nullptr, (int)h.batch, false);
+      }
+      return;
+    }
+    meta_copy_side(h);
+    {
+      PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
+      assemble_tiles(h, nullptr, (int)h.batch, false);
+    }
+  }
   DOPT_CHECK_HIP(hipEventSynchronize(h.meta_ev));
-  int npmax = 0;
+  int npmax = 0, nonsym = 0;
   h.has_generic = h.has_lsqr = false;
   for (int64_t b = 0; b < h.batch; ++b) {
     const QPMeta& mm = h.meta_host[b];
     const int r = qp_route(mm.iterative, mm.nsys);
-    if (r == ROUTE_BLOCKED) npmax = std::max(npmax, (mm.nsys + 31) & ~31);
+    if (r == ROUTE_BLOCKED) {
+      npmax = std::max(npmax, (mm.nsys + 31) & ~31);
+      nonsym += !mm.sym;
+    }
     h.has_generic |= r == ROUTE_GENERIC;
     h.has_lsqr |= r == ROUTE_LSQR;
   }
   h.blocked_npmax = npmax;
+  h.nonsym_blocked = nonsym;
+}
+
+// prepare of the whole batch for a factorisation.  Copy path: the metadata
+// read-back forks off right behind the prepare kernel (the host's wait
+// overlaps the tile kernel).  Returns whether the summary path was taken
+// (meta_sizes then queues the tiles).
+static bool prepare_batch(Handle& h) {
+  PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
+  if (h.batch == 0) return false;
+  const bool full = h.lu_mode == 0, summary = use_summary(h);
+  prepare(h, nullptr, (int)h.batch, full, summary);
+  if (!summary) {
+    meta_copy_side(h);
+    assemble_tiles(h, nullptr, (int)h.batch, full);
+  }
+  return summary;
 }
 
 // After the no-pivot LU: the problems it rejected, re-assembled (`reasm`) and
@@ -890,11 +983,8 @@ static ReasmFn qp_reasm(Handle& h) {
 void qp_factor(Handle& h) {
   if (!h.set) throw Error(-1, "dopt_qp_factor: dopt_qp_set has not been called");
   h.small_ready = false;   // K is overwritten
-  {
-    PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
-    prep_assemble(h, nullptr, (int)h.batch, h.lu_mode == 0, [&] { meta_copy_side(h); });
-  }
-  meta_sizes(h);
+  const bool summarised = prepare_batch(h);
+  meta_sizes(h, summarised);
   factor_blocked(h, [] {}, nullptr, nullptr, qp_reasm(h));
   h.factored = true;
 }
@@ -1144,10 +1234,7 @@ void qp_forward_reverse(Handle& h, const double* dl_dz, const double* dQ,
                         double* out_fwd) {
   if (!h.set) throw Error(-1, "dopt_qp_forward_reverse: dopt_qp_set has not been called");
   const FwdTangents T = tangents(h, dQ, dq, dG, dh, dA, db);
-  {
-    PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
-    prep_assemble(h, nullptr, (int)h.batch, h.lu_mode == 0, [&] { meta_copy_side(h); });
-  }
+  const bool summarised = prepare_batch(h);
   // no-pivot LU: both right-hand sides ride along as a bordering column / row
   // and come out forward-swept (w0, w1, written by the RHS kernels next to
   // rhs), leaving the solves the backward sweeps; rhs itself stays intact for
@@ -1161,7 +1248,7 @@ void qp_forward_reverse(Handle& h, const double* dl_dz, const double* dQ,
   }
   rev_rhs(h, dl_dz, w0);
   fwd_rhs(h, T, w1);
-  meta_sizes(h);
+  meta_sizes(h, summarised);
   if (!h.blocked_npmax) w0 = w1 = nullptr;
   auto solve2 = [&](int sel, const double* sw0, const double* sw1) {
     PhaseTimer pt(h, DOPT_PHASE_QP_SOLVE);

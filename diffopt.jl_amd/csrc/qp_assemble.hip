@@ -79,10 +79,12 @@ __global__ __launch_bounds__(PREP_MAXT, 3) void qp_prep_kernel(QPIn P, double* _
                                                             double* __restrict__ kls, double* __restrict__ gk,
                                                             int64_t B, QPMeta* __restrict__ meta,
                                                             const int32_t* __restrict__ plist,
-                                                            double* __restrict__ kamax, int sym_mode) {
+                                                            double* __restrict__ kamax, int sym_mode,
+                                                            QPSummary* sum, unsigned* arrive, unsigned epoch) {
   extern __shared__ __attribute__((aligned(16))) double zdyn[];
   __shared__ int cnt[PREP_MAXT / 64 + 1], scnt[PREP_MAXT / 64 + 1];
   __shared__ int extra, asym;
+  __shared__ int sred[5];   // the last workgroup's summary: npmax, generic, LSQR, non-symmetric count; "I am last"
   __shared__ double kred[PREP_MAXT / 64];
   double kmx = 0.0;   // max |K| over this thread's kept rows: |G_ij|, |λ_i G_ij|, |s_i|
   const int t = threadIdx.x, lane = t & 63, wv = t >> 6;
@@ -300,11 +302,66 @@ __global__ __launch_bounds__(PREP_MAXT, 3) void qp_prep_kernel(QPIn P, double* _
     meta[b].sym = sym_mode && !asym && qp_route(iterative, n + nk + p) == ROUTE_BLOCKED;
     kamax[b] = kmx;   // the tile kernel folds in max |Q| and |A|
   }
+  // Whole-batch launch (sum set): the last workgroup to arrive reduces every
+  // problem's metadata to what the host sizes the factorisation from and
+  // writes it to pinned memory.  Arrival counter: thread 0 stores its
+  // problem's (nsys, iterative, sym) as one write-through 8-byte word of
+  // `pack`, drains the store and takes a ticket; the workgroup that draws the
+  // last one acquires and reads every word with agent-scope loads.  (An
+  // agent-scope release fence per workgroup instead — a write-back of the
+  // XCD's L2, which holds the G_k copy's dirty lines — cost the prepare kernel
+  // 76 µs on config 2.)  Nobody waits on the device; the counter goes back to
+  // 0 for the next launch.
+  if (!sum) return;
+  unsigned long long* pack = reinterpret_cast<unsigned long long*>(arrive + 4);
+  if (t == 0) {
+    const int nsys = n + cnt[NW] + p;
+    const int sy = sym_mode && !asym && qp_route(iterative, nsys) == ROUTE_BLOCKED;
+    __hip_atomic_store(pack + b, (unsigned long long)(unsigned)nsys | (unsigned long long)(iterative | sy << 1) << 32,
+                       __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the word is written through before the ticket
+    const unsigned tk = __hip_atomic_fetch_add(arrive, 1u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int last = tk + 1 == gridDim.x;
+    if (last) {
+      __hip_atomic_store(arrive, 0u, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+      __builtin_amdgcn_fence(__ATOMIC_ACQUIRE, "agent");
+      asm volatile("s_waitcnt vmcnt(0)" ::: "memory");   // the invalidate lands before the barrier below
+    }
+    sred[0] = sred[1] = sred[2] = sred[3] = 0;
+    sred[4] = last;
+  }
+  __syncthreads();
+  if (!sred[4]) return;   // workgroup-uniform
+  int np = 0, gen = 0, lsq = 0, ns = 0;
+  for (int64_t i = t; i < B; i += T) {
+    const unsigned long long w = __hip_atomic_load(pack + i, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+    const int nsys = (int)(unsigned)w, fl = (int)(w >> 32);
+    const int r = qp_route(fl & 1, nsys);
+    if (r == ROUTE_BLOCKED) {
+      np = max(np, (nsys + 31) & ~31);
+      ns += !(fl & 2);
+    }
+    gen |= r == ROUTE_GENERIC;
+    lsq |= r == ROUTE_LSQR;
+  }
+  if (np) atomicMax(&sred[0], np);
+  if (gen) atomicOr(&sred[1], 1);
+  if (lsq) atomicOr(&sred[2], 1);
+  if (ns) atomicAdd(&sred[3], ns);
+  __syncthreads();
+  if (t == 0) {
+    __hip_atomic_store(&sum->blocked_npmax, sred[0], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&sum->has_generic, sred[1], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&sum->has_lsqr, sred[2], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    __hip_atomic_store(&sum->nonsym_blocked, sred[3], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_SYSTEM);
+    // the host polls this word: the release orders the four stores before it
+    __hip_atomic_store(&sum->done, epoch, __ATOMIC_RELEASE, __HIP_MEMORY_SCOPE_SYSTEM);
+  }
 }
 template __global__ void qp_prep_kernel<1>(QPIn, double*, int32_t*, int32_t*, double*, double*, int64_t, QPMeta*,
-                                           const int32_t*, double*, int);
+                                           const int32_t*, double*, int, QPSummary*, unsigned*, unsigned);
 template __global__ void qp_prep_kernel<2>(QPIn, double*, int32_t*, int32_t*, double*, double*, int64_t, QPMeta*,
-                                           const int32_t*, double*, int);
+                                           const int32_t*, double*, int, QPSummary*, unsigned*, unsigned);
 
 int prep_rows_per_thread(int m) { return (m % 2 == 0) ? 2 : 1; }
 int prep_threads(int m) {

@@ -69,8 +69,14 @@
 #ifndef NLU_STOP
 #define NLU_STOP 99
 #endif
-#ifndef NLU_ROT
-#define NLU_ROT (blockIdx.x & 3)
+// The elimination role of wave w (which 16 rows it holds, which single-wave
+// phase it runs): the wave index.  The hardware starts the four waves of the
+// workgroups sharing a CU on rotating SIMDs, so the role == q waves of
+// co-resident workgroups already sit on four different SIMDs (measured with
+// tools/probe/ldiag_probe.hip -DLDIAG_PLACE, which puts other mappings here;
+// DESIGN.md §6).
+#ifndef NLU_ROLE
+#define NLU_ROLE(w) (w)
 #endif
 // probe builds with -DNLU_STAMPS: per-phase s_memtime cycles of the diagonal
 // kernel summed over workgroups into nlu_stamps[] (thread 0)
@@ -99,6 +105,29 @@ __device__ unsigned long long ld_stamps[4096 * 16];
   } while (0)
 #else
 #define LD_MARK(k) do {} while (0)
+#endif
+// probe builds with -DLDIAG_PLACE: every wave of the left-looking diagonal
+// kernel records where it runs — the raw hardware-id, LDS-allocation and
+// XCC-id registers (named through the assembler) — and its role, per
+// workgroup and wave (lane 0, plain stores)
+#ifdef LDIAG_PLACE
+__device__ unsigned ld_place[4096 * 16];
+#define LD_PLACE(role)                                                                   \
+  do {                                                                                   \
+    if ((threadIdx.x & 63) == 0) {                                                       \
+      unsigned hw_, la_, xc_;                                                            \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw_));                  \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_LDS_ALLOC)" : "=s"(la_));              \
+      asm volatile("s_getreg_b32 %0, hwreg(HW_REG_XCC_ID)" : "=s"(xc_));                 \
+      unsigned* pl_ = ld_place + (blockIdx.x * 4 + (threadIdx.x >> 6)) * 4;              \
+      pl_[0] = hw_;                                                                      \
+      pl_[1] = la_;                                                                      \
+      pl_[2] = xc_;                                                                      \
+      pl_[3] = (unsigned)(role);                                                         \
+    }                                                                                    \
+  } while (0)
+#else
+#define LD_PLACE(role) do {} while (0)
 #endif
 
 namespace dopt {
@@ -684,9 +713,7 @@ __device__ __forceinline__ void diag_core(const DiagLds& L, double* __restrict__
   double* S = L.S;
   const int Wv = min(NB64, Np - c0);   // 32 or 64
   const bool trsm = Np - c0 > NB64;    // a trailing step follows
-  // wave roles rotate with the problem index, so that the single-wave phases
-  // (A, D) of the four workgroups sharing a CU land on different SIMDs
-  const int t = threadIdx.x, lane = t & 63, wv = ((t >> 6) + NLU_ROT) & 3;
+  const int t = threadIdx.x, lane = t & 63, wv = NLU_ROLE(t >> 6);
   const int g = lane >> 4, l16 = lane & 15;
   NLU_MARK_INIT;
   if (t == 0) *L.sbad = 0;
@@ -1635,7 +1662,8 @@ __device__ __forceinline__ void ldl64_core(double* buf, double* __restrict__ Kb,
   int* sbad = reinterpret_cast<int*>(P + 320);
   const int Wv = min(NB64, Np - c0);   // 32 or 64: identity beyond
   const bool trsm = Np - c0 > NB64;
-  const int t = threadIdx.x, lane = t & 63, role = ((t >> 6) + NLU_ROT) & 3;
+  const int t = threadIdx.x, lane = t & 63, role = NLU_ROLE(t >> 6);
+  LD_PLACE(role);
   if (t < 64) {
     const double p = ps(c0 + t);
     P[t] = p;
@@ -2307,7 +2335,8 @@ void qp_nopiv_factor(Handle& h, double* dinv, double* w0, double* w1) {
   const bool qp = h.kind == DOPT_KIND_QP;
   const double* kls = qp ? h.kls.as<double>() : nullptr;
   double* kamax = h.kamax.as<double>();
-  int lower = qp && h.meta_host ? 1 : 0;
+  // (the count of the others: meta_sizes, from this call's metadata)
+  const int lower = qp && h.nonsym_blocked == 0 ? 1 : 0;
   // step 0 of the P-symmetric problems reads the QP inputs (no K assembly)
   static const double zero = 0.0;
   QSrc src;
@@ -2324,14 +2353,6 @@ void qp_nopiv_factor(Handle& h, double* dinv, double* w0, double* w1) {
   src.p = h.p;
   src.B = h.batch;
   const int srcmode = qp ? 1 : 0;
-  if (lower)
-    for (int64_t b = 0; b < h.batch; ++b) {
-      const QPMeta& mm = h.meta_host[b];
-      if (qp_route(mm.iterative, mm.nsys) == ROUTE_BLOCKED && !mm.sym) {
-        lower = 0;
-        break;
-      }
-    }
   const size_t dstride = dinv_stride(h.nmax);
   double* K = h.K.as<double>();
   int32_t* perm = h.ipiv.as<int32_t>();

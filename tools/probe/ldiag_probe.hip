@@ -5,13 +5,40 @@
 // at LD_MARK k, averaged over the workgroups of each launch).
 //   hipcc --offload-arch=gfx950 -O3 -DLDIAG_STAMPS tools/probe/ldiag_probe.hip -o ldiag
 //   ./ldiag B NP
+// With -DLDIAG_PLACE every wave of the first diagonal launch also records its
+// hardware-id, LDS-allocation and XCC-id registers and its role (raw values
+// of a few workgroups are printed, so the field layout can be checked), and
+// the probe prints, per elimination phase q, how many CUs have their
+// role == q waves on 1, 2, 3 or 4 distinct SIMDs.  A third argument selects
+// the role: 0 the rotation (wave + blockIdx.x) & 3 the product used until
+// this probe showed it idle, 1 the placement-derived (SIMD id + LDS slot) & 3
+// — probe only: it has no fallback for a workgroup whose waves share a SIMD
+// (such workgroups are counted and reported) —, 2 the wave index itself.
+//   ./ldiag B NP [0|1|2]
+#include <hip/hip_runtime.h>
+#ifdef LDIAG_PLACE
+__device__ unsigned probe_role_cfg[2];   // [0] role mode, [1] LDS-base units per workgroup allocation
+__device__ __forceinline__ int probe_role(int w) {
+  if (!probe_role_cfg[0]) return (w + (int)(blockIdx.x & 3)) & 3;
+  if (probe_role_cfg[0] == 2) return w;
+  unsigned hw, la;
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_HW_ID)" : "=s"(hw));
+  asm volatile("s_getreg_b32 %0, hwreg(HW_REG_LDS_ALLOC)" : "=s"(la));
+  return (int)((((hw >> 4) & 3) + (la & 0xfff) / probe_role_cfg[1]) & 3);
+}
+#define NLU_ROLE(w) probe_role(w)
+#endif
 #include "../../diffopt.jl_amd/csrc/qp_nopiv.hip"
+#include <algorithm>
 #include <cstdio>
 #include <cstdlib>
+#include <map>
+#include <set>
 #include <vector>
 
 namespace dopt {
 size_t dinv_stride(int nmax) { return (size_t)((nmax + 31) / 32) * 2 * 32 * 32; }
+double* dense_dinv(Handle&) { return nullptr; }   // (qp_nopiv_materialize_u: unused here)
 // the NLP route's host helpers (unused here)
 NLPDims nlp_dims(const Handle&) { return NLPDims{}; }
 NLPIn nlp_inputs(const Handle&) { return NLPIn{}; }
@@ -73,6 +100,53 @@ int main(int argc, char** argv) {
   std::vector<unsigned long long> st((size_t)B * 16);
   std::vector<double> stsum((size_t)nb * 16, 0.0);
   const int reps = 10;
+#ifdef LDIAG_PLACE
+  if (B > 4096) return 1;   // ld_place holds 4096 workgroups
+  const unsigned mode = argc > 3 ? (unsigned)atoi(argv[3]) : 0u;
+  std::vector<unsigned> pl((size_t)B * 16);
+  // field layout (gfx9 family; check against the raw values printed below):
+  // HW_ID simd [5:4], cu / sh / se [15:8]; LDS_ALLOC base [7:0] (read as [11:0])
+  auto cu_of = [&](int b) { return ((unsigned long long)pl[(size_t)b * 16 + 2] << 32) | (pl[(size_t)b * 16] & 0xff00u); };
+  auto base_of = [&](int b) { return pl[(size_t)b * 16 + 1] & 0xfffu; };
+  auto read_place = [&] {
+    hipDeviceSynchronize();
+    hipMemcpyFromSymbol(pl.data(), HIP_SYMBOL(ld_place), (size_t)B * 16 * 4);
+  };
+  unsigned cfg[2] = {0u, 1u};
+  hipMemcpyToSymbol(HIP_SYMBOL(probe_role_cfg), cfg, sizeof(cfg));
+  {
+    // one launch with the product's roles: the LDS-base step between the
+    // workgroups sharing a CU sizes the slot
+    hipMemcpy(meta, hm.data(), B * sizeof(QPMeta), hipMemcpyHostToDevice);
+    hipLaunchKernelGGL((nlu_ldiag_kernel<QSrc>), dim3(B), dim3(PNT), 0, 0, K, ld, nmax, perm, dinv, dinv_stride(nmax),
+                       meta, 0, binv, ukp, nullptr, nullptr, kamax, nullptr, n, 0, src, 0);
+    read_place();
+    std::map<unsigned long long, std::set<unsigned>> bases;
+    for (int b = 0; b < B; ++b) bases[cu_of(b)].insert(base_of(b));
+    unsigned step = 0;
+    for (auto& kv : bases) {
+      unsigned prev = 0;
+      bool first = true;
+      for (unsigned v : kv.second) {
+        if (!first && (step == 0 || v - prev < step)) step = v - prev;
+        prev = v;
+        first = false;
+      }
+    }
+    printf("placement: %zu CUs hold the %d workgroups; smallest LDS-base step on a CU %u\n", bases.size(), B, step);
+    for (int b = 0; b < B && b < 4; ++b)
+      for (int w = 0; w < 4; ++w)
+        printf("  raw wg %d wave %d: HW_ID %08x LDS_ALLOC %08x XCC_ID %08x role %u\n", b, w, pl[(size_t)b * 16 + 4 * w],
+               pl[(size_t)b * 16 + 4 * w + 1], pl[(size_t)b * 16 + 4 * w + 2], pl[(size_t)b * 16 + 4 * w + 3]);
+    if (mode && step == 0) {
+      printf("no two workgroups share a CU: the slot is 0, roles = SIMD id\n");
+      step = 0xfff + 1;
+    }
+    cfg[0] = mode;
+    cfg[1] = step ? step : 1u;
+    hipMemcpyToSymbol(HIP_SYMBOL(probe_role_cfg), cfg, sizeof(cfg));
+  }
+#endif
   for (int r = 0; r <= reps; ++r) {
     hipMemcpy(meta, hm.data(), B * sizeof(QPMeta), hipMemcpyHostToDevice);
     hipDeviceSynchronize();
@@ -83,6 +157,41 @@ int main(int argc, char** argv) {
       hipLaunchKernelGGL((nlu_ldiag_kernel<QSrc>), dim3(B), dim3(PNT), 0, 0, K, ld, nmax, perm, dinv,
                          dinv_stride(nmax), meta, c0, bv, ukp, nullptr, nullptr, kamax, nullptr, n, 0, src, 0);
       hipEventRecord(ev[e++]);
+#ifdef LDIAG_PLACE
+      if (r == reps && J == 0) {
+        read_place();
+        // per CU and phase q: the SIMDs of the role == q waves of its workgroups
+        std::map<unsigned long long, std::vector<int>> wgs;
+        for (int b = 0; b < B; ++b) wgs[cu_of(b)].push_back(b);
+        int shared_simd = 0, dup_role = 0, hist[4][5] = {}, per_cu[8] = {};
+        for (int b = 0; b < B; ++b) {
+          std::set<unsigned> sd, rl;
+          for (int w = 0; w < 4; ++w) {
+            sd.insert((pl[(size_t)b * 16 + 4 * w] >> 4) & 3);
+            rl.insert(pl[(size_t)b * 16 + 4 * w + 3]);
+          }
+          shared_simd += sd.size() != 4;
+          dup_role += rl.size() != 4;
+        }
+        for (auto& kv : wgs) {
+          per_cu[std::min<size_t>(kv.second.size(), 7)]++;
+          for (unsigned q = 0; q < 4; ++q) {
+            std::set<unsigned> sd;
+            for (int b : kv.second)
+              for (int w = 0; w < 4; ++w)
+                if (pl[(size_t)b * 16 + 4 * w + 3] == q) sd.insert((pl[(size_t)b * 16 + 4 * w] >> 4) & 3);
+            hist[q][std::min<size_t>(sd.size(), 4)]++;
+          }
+        }
+        printf("role mode %u: workgroups whose waves share a SIMD %d, with a repeated role %d\n", mode, shared_simd, dup_role);
+        printf("CUs by resident workgroups:");
+        for (int k = 1; k < 8; ++k) printf(" %d:%d", k, per_cu[k]);
+        printf("\n");
+        for (int q = 0; q < 4; ++q)
+          printf("phase %d: CUs whose role == %d waves sit on 1 / 2 / 3 / 4 distinct SIMDs: %d / %d / %d / %d\n", q, q,
+                 hist[q][1], hist[q][2], hist[q][3], hist[q][4]);
+      }
+#endif
 #ifdef LDIAG_STAMPS
       if (r == reps) {
         hipDeviceSynchronize();
