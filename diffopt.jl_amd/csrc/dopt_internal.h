@@ -132,6 +132,9 @@ __host__ __device__ inline int qp_route(int iterative, int nsys) {
   if (nsys <= BLOCKED_MAX) return ROUTE_BLOCKED;
   return ROUTE_GENERIC;
 }
+// The padded size of a factorised system: the blocked kernels work on whole
+// 32-row blocks.
+__host__ __device__ inline int padded32(int nsys) { return (nsys + 31) & ~31; }
 
 // The no-pivot LU accepts a problem's factors only while every multiplier
 // satisfies |l_ij| ≤ NOPIV_LMAX, i.e. the diagonal passes the threshold test
@@ -255,7 +258,7 @@ struct Handle {
   DevBuf mws;                // multi-RHS: per-workgroup vectors of tall systems (qp_multi.hip)
   QPMeta* meta_host = nullptr;     // pinned copy of `meta` (asynchronous read-back)
   hipEvent_t meta_ev = nullptr;    // recorded after the read-back copy
-  hipEvent_t meta_fork = nullptr;  // the LU's end on the handle's stream (the read-back on `aux` waits for it)
+  hipEvent_t meta_fork = nullptr;  // the read-back's fork point on the handle's stream (the copy on `crit` waits for it)
   // the prepare kernel's summary of a whole batch's metadata (QPSummary, pinned
   // and coherent: the host polls it instead of copying `meta` back); env
   // DOPT_QP_SUMMARY=0: the copy of every QPMeta and the host's loops over it
@@ -496,15 +499,37 @@ void qp_blocked_solve2(Handle& h, const double* dinv, const double* rhs_rev, con
 size_t dinv_stride(int nmax);
 // re-assembly of a list of problems (plist: device indices, count)
 using ReasmFn = std::function<void(const int32_t*, int)>;
-// pre_copy (optional): launched after the no-pivot LU, before its metadata
-// read-back (so the host's copy carries what it writes)
-// deferred (optional): with every problem on the no-pivot blocked route the
-// call returns with the LU queued and its metadata read-back in flight
-// (*deferred = true); factor_dense_finish does the rest
-void factor_dense(Handle& h, const ReasmFn& reasm, const std::function<void()>* pre_copy = nullptr,
-                  bool* deferred = nullptr);
+// What a blocked factorisation takes from its caller (qp.hip factor_blocked).
+struct FactorOpts {
+  int32_t lu_mode = 1;                  // as Handle::lu_mode; the call reads this one, not the handle's
+  double *w0 = nullptr, *w1 = nullptr;  // fused call: the right-hand sides the no-pivot LU forward-sweeps
+  ReasmFn reasm;                        // re-assembly of the problems the no-pivot LU rejects
+  std::function<void()> pre_readback;   // optional: launched after the no-pivot LU, before its metadata
+                                        // read-back (so the host's copy carries what it writes)
+  bool may_defer = false;               // with every problem on the no-pivot blocked route the call may return
+                                        // with the LU queued and its read-back in flight (Deferred)
+};
+enum class Factored { Done, Deferred };
+// What the host needs of a batch's routes to size the factorisation
+// (QPSummary's four values), from a host copy of its metadata.
+struct RouteScan {
+  int32_t blocked_npmax = 0, nonsym_blocked = 0;
+  bool has_generic = false, has_lsqr = false;
+};
+RouteScan scan_routes(const QPMeta* meta, int64_t count);
+// Asynchronous upload of a host index list into `buf` on the handle's stream;
+// returns the device list.  `list` must outlive the copy: the caller
+// synchronises the stream before `list` goes out of scope or changes.
+const int32_t* upload_list(Handle& h, DevBuf& buf, const std::vector<int32_t>& list);
+// The blocked factorisation of a batch already assembled into K / meta by a
+// caller (the NLP back-end).  Sizes from h.blocked_npmax; blocked route only.
+// Deferred: factor_dense_finish does the rest (the wait for the read-back,
+// then the rejected problems' fallbacks).
+Factored factor_dense(Handle& h, const FactorOpts& o);
 void factor_dense_finish(Handle& h, const ReasmFn& reasm);
 double* dense_dinv(Handle& h);
+// LSQR (IterativeSolvers defaults) on the K slabs of the problems whose
+// meta.iterative is set: rhs / x stride nmax per problem
 void lsqr_slabs(Handle& h, int trans, const double* rhs, double* x);
 void lhs_solve(Handle& h, int k, const double* rhs, double* x, bool iterative, int32_t* info);
 void lhs_resolve(Handle& h, int k, const double* rhs, double* x, bool trans, int32_t* info);

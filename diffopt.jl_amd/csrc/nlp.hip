@@ -176,7 +176,7 @@ __global__ __launch_bounds__(NT) void nlp_assemble_kernel(NLPDims d, NLPMap mp, 
   const size_t bb = (size_t)b;
   const bool reduced = red_use(Rd, shift, b);   // workgroup-uniform
   const int rows = reduced ? d.n + d.c : d.rows;
-  const int Np = (rows + 31) & ~31;
+  const int Np = padded32(rows);
   const int kc = max(shift[b], 0);
   const int lo0 = d.num_w + d.c, up0 = lo0 + d.nlo;
   double* Kb = K + bb * nmax * ld;
@@ -828,7 +828,7 @@ NLPIn inputs(const Handle& h) {
   return in;
 }
 
-int row_blocks(const Handle& h) { return (((h.nlp_rows + 31) & ~31) + ROWS_PER_WG - 1) / ROWS_PER_WG; }
+int row_blocks(const Handle& h) { return (padded32(h.nlp_rows) + ROWS_PER_WG - 1) / ROWS_PER_WG; }
 
 // the reduced route's per-problem data (on: structured mode and nlp_reduce)
 NLPRed red_of(Handle& h) {
@@ -1021,7 +1021,7 @@ void nlp_factor(Handle& h, bool defer, bool spec_ok) {
       DOPT_CHECK_HIP(hipGetLastError());
       if (spec) {
         const NLPDims d = dims(h);
-        h.blocked_npmax = (d.n + d.c + 31) & ~31;
+        h.blocked_npmax = padded32(d.n + d.c);
         h.nlp_left = true;
       } else {
         // the factorised sizes (n + c, or the rows of M for a problem kept on
@@ -1030,10 +1030,9 @@ void nlp_factor(Handle& h, bool defer, bool spec_ok) {
         std::vector<QPMeta> mh(B);
         DOPT_CHECK_HIP(hipMemcpyAsync(mh.data(), h.meta.p, B * sizeof(QPMeta), hipMemcpyDeviceToHost, h.stream));
         DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
-        int npmax = 0;
-        for (const QPMeta& mm : mh) npmax = std::max(npmax, (mm.nsys + 31) & ~31);
-        h.blocked_npmax = npmax;
-        h.nlp_left = hasym && std::all_of(mh.begin(), mh.end(), [](const QPMeta& mm) { return mm.sym != 0; });
+        const RouteScan rs = scan_routes(mh.data(), B);   // (every problem is blocked: nlp_configure's cap)
+        h.blocked_npmax = rs.blocked_npmax;
+        h.nlp_left = hasym && rs.nonsym_blocked == 0;
       }
     }
     if (!h.nlp_left)   // (none: the pivot check's scale is nlp_mscale alone, the zeroed rows)
@@ -1054,41 +1053,34 @@ void nlp_factor(Handle& h, bool defer, bool spec_ok) {
   // pivoting for what its tests reject.
   const bool saddle_only = (!h.nlp_kkt && h.nlp_ng + h.nlp_nl + h.nlp_nlo + h.nlp_nup == 0) ||
                            (h.nlp_kkt && h.nlp_max_corr == 0);
-  const int32_t lu_mode = h.lu_mode;
-  if (!saddle_only && !reduced_on(h)) h.lu_mode = 0;
+  FactorOpts o;
+  o.lu_mode = !saddle_only && !reduced_on(h) ? 0 : h.lu_mode;
+  o.reasm = [&h](const int32_t* pl, int count) { assemble(h, pl, count); };
   // the singularity check rides on the LU's metadata read-back when the
   // no-pivot LU accepted every problem (one host turnaround instead of two)
   bool early_check = false;
-  const std::function<void()> pre = [&] {
+  o.pre_readback = [&] {
     pivot_check(h, nullptr, B);
     early_check = true;
   };
-  bool fast = false, deferred = false;
-  try {
-    // (a speculative launch always defers: the guess is checked before any
-    // fallback reads the metadata)
-    factor_dense(h, [&h](const int32_t* pl, int count) { assemble(h, pl, count); }, &pre,
-                 defer || spec ? &deferred : nullptr);
-    if (spec && !deferred) throw Error(-1, "dopt_nlp_factor: internal: speculative LU not deferred");
-    if (deferred) {   // the verdicts are read back by the next call that needs the factors (nlp_finish)
-      h.nlp_fast_ok = early_check && h.lu_mode == 1;
-      h.lu_mode = lu_mode;
-      h.nlp_pending = true;
-      h.nlp_spec = spec;
-      h.nfactored = true;
-      if (!defer) nlp_finish(h);
-      return;
-    }
-    // (a rejected problem too tall for the pivoting panel goes to the generic
-    // LU, counted in n_generic, not n_pivot: its factor was not seen by the
-    // early check — ADVICE r04)
-    fast = early_check && h.lu_mode == 1 && h.n_pivot == 0 && h.n_generic == 0 && h.blocked_npmax > 0 &&
-           h.meta_host;
-  } catch (...) {
-    h.lu_mode = lu_mode;
-    throw;
+  // (a speculative launch always defers: the guess is checked before any
+  // fallback reads the metadata)
+  o.may_defer = defer || spec;
+  const bool deferred = factor_dense(h, o) == Factored::Deferred;
+  if (spec && !deferred) throw Error(-1, "dopt_nlp_factor: internal: speculative LU not deferred");
+  if (deferred) {   // the verdicts are read back by the next call that needs the factors (nlp_finish)
+    h.nlp_fast_ok = early_check && o.lu_mode == 1;
+    h.nlp_pending = true;
+    h.nlp_spec = spec;
+    h.nfactored = true;
+    if (!defer) nlp_finish(h);
+    return;
   }
-  h.lu_mode = lu_mode;
+  // (a rejected problem too tall for the pivoting panel goes to the generic
+  // LU, counted in n_generic, not n_pivot: its factor was not seen by the
+  // early check — ADVICE r04)
+  const bool fast = early_check && o.lu_mode == 1 && h.n_pivot == 0 && h.n_generic == 0 && h.blocked_npmax > 0 &&
+                    h.meta_host;
   nlp_factor_tail(h, fast);
 }
 
@@ -1146,13 +1138,11 @@ static void nlp_factor_tail(Handle& h, bool fast) {
     for (int32_t b : sing) shift[b] = k;
     DOPT_CHECK_HIP(hipMemcpyAsync(h.nlp_shift.p, shift.data(), (size_t)B * sizeof(int32_t), hipMemcpyHostToDevice,
                                   h.stream));
-    h.plist.ensure(sing.size() * sizeof(int32_t));
-    DOPT_CHECK_HIP(hipMemcpyAsync(h.plist.p, sing.data(), sing.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                  h.stream));
+    const int32_t* pl = upload_list(h, h.plist, sing);
     h.blocked_npmax = h.nmax;   // the corrected problems are the full M
-    assemble(h, h.plist.as<int32_t>(), (int)sing.size());
-    qp_blocked_factor(h, dense_dinv(h), h.plist.as<int32_t>(), (int)sing.size());
-    pivot_check(h, h.plist.as<int32_t>(), (int)sing.size());
+    assemble(h, pl, (int)sing.size());
+    qp_blocked_factor(h, dense_dinv(h), pl, (int)sing.size());
+    pivot_check(h, pl, (int)sing.size());
     std::vector<int32_t> still = singular_list(h, sing);   // synchronises: the uploads are done
     for (int32_t b : sing) h.nlp_corr[b] = k;
     sing.swap(still);

@@ -748,24 +748,13 @@ static void prep_assemble(Handle& h, const int32_t* plist, int count) {
   assemble_tiles(h, plist, count, true);
 }
 
-// Asynchronous read-back of the per-problem metadata into pinned memory; the
-// caller may queue independent kernels before waiting (meta_wait), so the
-// host turnaround overlaps them.
-static void meta_copy(Handle& h) {
-  if (!h.meta_host) {
-    DOPT_CHECK_HIP(hipHostMalloc((void**)&h.meta_host, std::max<size_t>(h.batch, 1) * sizeof(QPMeta)));
-    DOPT_CHECK_HIP(hipEventCreateWithFlags(&h.meta_ev, hipEventDisableTiming));
-  }
-  DOPT_CHECK_HIP(hipMemcpyAsync(h.meta_host, h.meta.p, h.batch * sizeof(QPMeta), hipMemcpyDeviceToHost,
-                                h.stream));
-  DOPT_CHECK_HIP(hipEventRecord(h.meta_ev, h.stream));
-}
-
-// The same read-back on a side stream, forked from the handle's stream by a
-// device-scope event: the kernels queued next on the handle's stream (the
-// assembly tiles after the prepare kernel, the speculative solves after the
-// LU) do not wait behind the copy.
-static void meta_copy_side(Handle& h) {
+// Asynchronous read-back of the per-problem metadata into pinned memory
+// (meta_host; meta_ev once it has landed), on a side stream forked from the
+// handle's stream by a device-scope event: the kernels queued next on the
+// handle's stream (the assembly tiles after the prepare kernel, the
+// speculative solves after the LU) do not wait behind the copy, and the
+// host's turnaround overlaps them.
+static void meta_readback(Handle& h) {
   ensure_aux(h);
   if (!h.meta_host) {
     DOPT_CHECK_HIP(hipHostMalloc((void**)&h.meta_host, std::max<size_t>(h.batch, 1) * sizeof(QPMeta)));
@@ -796,86 +785,114 @@ static void summary_wait(Handle& h) {
     throw Error(-1, "QP prepare: the batch summary was not written");
 }
 
-// After the prepare kernel: largest padded blocked system (sizes the blocked
-// launches), whether any problem needs the generic or the LSQR kernels, how
-// many blocked problems are not P-symmetric — from the kernel's summary
-// (`summarised`: prepare ran with one; the assembly tiles are then queued
-// here, and only if some problem is assembled at all), else from the copy of
-// every QPMeta.  A batch with generic problems takes the copy as well: the
-// host lists them per problem (factor_blocked).
-static void meta_sizes(Handle& h, bool summarised) {
-  if (summarised) {
-    summary_wait(h);
-    const QPSummary& sm = *h.qsum;
-    if (!sm.has_generic) {
-      h.blocked_npmax = sm.blocked_npmax;
-      h.has_generic = false;
-      h.has_lsqr = sm.has_lsqr != 0;
-      h.nonsym_blocked = sm.nonsym_blocked;
-      if (sm.nonsym_blocked || sm.has_lsqr) {   // else every problem is P-symmetric: no tile is written
-        PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
-        assemble_tiles(h, nullptr, (int)h.batch, false);
-      }
-      return;
-    }
-    meta_copy_side(h);
-    {
-      PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
-      assemble_tiles(h, nullptr, (int)h.batch, false);
-    }
-  }
-  DOPT_CHECK_HIP(hipEventSynchronize(h.meta_ev));
-  int npmax = 0, nonsym = 0;
-  h.has_generic = h.has_lsqr = false;
-  for (int64_t b = 0; b < h.batch; ++b) {
-    const QPMeta& mm = h.meta_host[b];
+// Largest padded blocked system (sizes the blocked launches), whether any
+// problem needs the generic or the LSQR kernels, how many blocked problems are
+// not P-symmetric: the host's restatement of the prepare kernel's QPSummary.
+RouteScan scan_routes(const QPMeta* meta, int64_t count) {
+  RouteScan rs;
+  for (int64_t b = 0; b < count; ++b) {
+    const QPMeta& mm = meta[b];
     const int r = qp_route(mm.iterative, mm.nsys);
     if (r == ROUTE_BLOCKED) {
-      npmax = std::max(npmax, (mm.nsys + 31) & ~31);
-      nonsym += !mm.sym;
+      rs.blocked_npmax = std::max(rs.blocked_npmax, padded32(mm.nsys));
+      rs.nonsym_blocked += !mm.sym;
     }
-    h.has_generic |= r == ROUTE_GENERIC;
-    h.has_lsqr |= r == ROUTE_LSQR;
+    rs.has_generic |= r == ROUTE_GENERIC;
+    rs.has_lsqr |= r == ROUTE_LSQR;
   }
-  h.blocked_npmax = npmax;
-  h.nonsym_blocked = nonsym;
+  return rs;
 }
 
-// prepare of the whole batch for a factorisation.  Copy path: the metadata
-// read-back forks off right behind the prepare kernel (the host's wait
-// overlaps the tile kernel).  Returns whether the summary path was taken
-// (meta_sizes then queues the tiles).
-static bool prepare_batch(Handle& h) {
-  PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
-  if (h.batch == 0) return false;
-  const bool full = h.lu_mode == 0, summary = use_summary(h);
-  prepare(h, nullptr, (int)h.batch, full, summary);
-  if (!summary) {
-    meta_copy_side(h);
-    assemble_tiles(h, nullptr, (int)h.batch, full);
+// prepare of the whole batch for a factorisation, in two halves around the
+// caller's own launches (the fused call's right-hand sides).
+//  - The constructor queues the prepare kernel.  Copy path: the metadata
+//    read-back forks off right behind it (the host's wait overlaps the tile
+//    kernel), then the tiles.  Summary path: neither yet.
+//  - wait_and_launch_tiles fills the handle's sizes (blocked_npmax,
+//    has_generic, has_lsqr, nonsym_blocked) from the kernel's summary and
+//    queues the tiles the summary path still owes — only if some problem is
+//    assembled at all — else from the copy of every QPMeta.  A summarised
+//    batch with generic problems takes the copy as well: the host lists them
+//    per problem (factor_blocked).
+// Which path the first half took stays inside the object.
+class BatchPrepareLaunch {
+ public:
+  explicit BatchPrepareLaunch(Handle& hh) : h(hh) {
+    PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
+    if (h.batch == 0) return;
+    const bool full = h.lu_mode == 0;
+    summarised = use_summary(h);
+    prepare(h, nullptr, (int)h.batch, full, summarised);
+    if (!summarised) {
+      meta_readback(h);
+      assemble_tiles(h, nullptr, (int)h.batch, full);
+    }
   }
-  return summary;
+  void wait_and_launch_tiles() {
+    if (summarised) {
+      summary_wait(h);
+      const QPSummary& sm = *h.qsum;
+      if (!sm.has_generic) {
+        RouteScan rs;
+        rs.blocked_npmax = sm.blocked_npmax;
+        rs.nonsym_blocked = sm.nonsym_blocked;
+        rs.has_lsqr = sm.has_lsqr != 0;
+        set_sizes(rs);
+        if (rs.nonsym_blocked || rs.has_lsqr) tiles();   // else every problem is P-symmetric: no tile is written
+        return;
+      }
+      meta_readback(h);
+      tiles();
+    }
+    DOPT_CHECK_HIP(hipEventSynchronize(h.meta_ev));
+    set_sizes(scan_routes(h.meta_host, h.batch));
+  }
+
+ private:
+  void tiles() {
+    PhaseTimer pt(h, DOPT_PHASE_QP_ASSEMBLE);
+    assemble_tiles(h, nullptr, (int)h.batch, false);
+  }
+  void set_sizes(const RouteScan& rs) {
+    h.blocked_npmax = rs.blocked_npmax;
+    h.nonsym_blocked = rs.nonsym_blocked;
+    h.has_generic = rs.has_generic;
+    h.has_lsqr = rs.has_lsqr;
+  }
+  Handle& h;
+  bool summarised = false;
+};
+
+const int32_t* upload_list(Handle& h, DevBuf& buf, const std::vector<int32_t>& list) {
+  buf.ensure(list.size() * sizeof(int32_t));
+  DOPT_CHECK_HIP(hipMemcpyAsync(buf.p, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice, h.stream));
+  return buf.as<int32_t>();
 }
 
-// After the no-pivot LU: the problems it rejected, re-assembled (`reasm`) and
+// The no-pivot LU's verdicts, from the read-back (after meta_ev): the rejected
+// problems the partial-pivoting panel takes (padded size ≤ PIVOT_MAX), and
+// those too tall for it (the generic LU).
+struct Rejected {
+  std::vector<int32_t> panel, tall;
+};
+static Rejected scan_rejected(const Handle& h) {
+  Rejected rej;
+  for (int64_t b = 0; b < h.batch; ++b) {
+    const QPMeta& mm = h.meta_host[b];
+    if (mm.lu != LU_REJECT) continue;
+    (padded32(mm.nsys) <= PIVOT_MAX ? rej.panel : rej.tall).push_back((int32_t)b);
+  }
+  return rej;
+}
+
+// The rejected problems in `list` (not empty), re-assembled (`reasm`) and
 // factorised with partial pivoting.  Returns their count.
-static int pivot_fallback(Handle& h, const ReasmFn& reasm) {
-  DOPT_CHECK_HIP(hipEventSynchronize(h.meta_ev));
-  std::vector<int32_t> list;
-  for (int64_t b = 0; b < h.batch; ++b)
-    if (h.meta_host[b].lu == LU_REJECT && ((h.meta_host[b].nsys + 31) & ~31) <= PIVOT_MAX)
-      list.push_back((int32_t)b);
+static int pivot_fallback(Handle& h, const ReasmFn& reasm, const std::vector<int32_t>& list) {
   const int count = (int)list.size();
-  if (count) {
-    h.plist.ensure(list.size() * sizeof(int32_t));
-    DOPT_CHECK_HIP(hipMemcpyAsync(h.plist.p, list.data(), list.size() * sizeof(int32_t),
-                                  hipMemcpyHostToDevice, h.stream));
-    const int32_t* pl = h.plist.as<int32_t>();
-    reasm(pl, count);
-    qp_blocked_factor(h, dinv_of(h), pl, count);
-    // the host copy of `list` must outlive the asynchronous upload
-    DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
-  }
+  const int32_t* pl = upload_list(h, h.plist, list);
+  reasm(pl, count);
+  qp_blocked_factor(h, dinv_of(h), pl, count);
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
   return count;
 }
 
@@ -883,49 +900,30 @@ static int pivot_fallback(Handle& h, const ReasmFn& reasm) {
 static void generic_lu(Handle& h, const std::vector<int32_t>& list) {
   h.n_generic = (int)list.size();
   if (list.empty()) return;
-  h.glist.ensure(list.size() * sizeof(int32_t));
-  DOPT_CHECK_HIP(hipMemcpyAsync(h.glist.p, list.data(), list.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                h.stream));
+  const int32_t* gl = upload_list(h, h.glist, list);
   hipLaunchKernelGGL(qp_lu_generic_kernel, dim3((unsigned)list.size()), dim3(TPB), 0, h.stream, h.K.as<double>(),
-                     h.ipiv.as<int32_t>(), h.meta.as<QPMeta>(), h.nmax, h.ld, h.glist.as<int32_t>());
+                     h.ipiv.as<int32_t>(), h.meta.as<QPMeta>(), h.nmax, h.ld, gl);
   check_launch();
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // `list` outlives the upload
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
 }
 
-// Factorisation of the assembled batch (prepare + assembly already queued and
-// the metadata read back).  Blocked problems: the no-pivot LU, then partial
-// pivoting for the problems it rejects (lu_mode 1), or partial pivoting for
-// all (lu_mode 0) — the partial-pivoting blocked LU up to PIVOT_MAX, the
-// generic LU above it (and for the ROUTE_GENERIC problems).  `spec`
-// (optional) is queued right after the no-pivot LU, before the host waits for
-// the rejected list: work that skips rejected problems (the solves of the
-// fused call).
-// After the no-pivot LU and its metadata read-back: the problems it rejected
-// (partial pivoting, re-assembled by `reasm`; those too tall for the pivoting
-// panel join `glist`), then the generic LU of `glist`.
+// After the blocked LU: with `nopiv` (the no-pivot LU ran, its metadata
+// read-back is in flight) the wait for the read-back, then the problems it
+// rejected — partial pivoting, re-assembled by `reasm`; those too tall for the
+// pivoting panel are re-assembled and join `glist` — then the generic LU of
+// `glist`.
 static void factor_blocked_rest(Handle& h, const ReasmFn& reasm, std::vector<int32_t>& glist, bool nopiv) {
-  auto np_of = [](const QPMeta& mm) { return (mm.nsys + 31) & ~31; };
   if (nopiv && h.blocked_npmax) {
     DOPT_CHECK_HIP(hipEventSynchronize(h.meta_ev));
-    bool any = false;
-    std::vector<int32_t> big;   // rejected problems too tall for the pivoting panel
-    for (int64_t b = 0; b < h.batch; ++b) {
-      const QPMeta& mm = h.meta_host[b];
-      if (mm.lu != LU_REJECT) continue;
-      if (np_of(mm) > PIVOT_MAX) big.push_back((int32_t)b);
-      else any = true;
-    }
-    if (any) {
+    const Rejected rej = scan_rejected(h);
+    if (!rej.panel.empty()) {
       PhaseTimer pt(h, DOPT_PHASE_QP_LU_PIVOT);
-      h.n_pivot = pivot_fallback(h, reasm);
+      h.n_pivot = pivot_fallback(h, reasm, rej.panel);
     }
-    if (!big.empty()) {
-      h.plist.ensure(big.size() * sizeof(int32_t));
-      DOPT_CHECK_HIP(hipMemcpyAsync(h.plist.p, big.data(), big.size() * sizeof(int32_t), hipMemcpyHostToDevice,
-                                    h.stream));
-      reasm(h.plist.as<int32_t>(), (int)big.size());
+    if (!rej.tall.empty()) {
+      reasm(upload_list(h, h.plist, rej.tall), (int)rej.tall.size());
       DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));
-      glist.insert(glist.end(), big.begin(), big.end());
+      glist.insert(glist.end(), rej.tall.begin(), rej.tall.end());
     }
   }
   h.n_generic = 0;
@@ -935,31 +933,35 @@ static void factor_blocked_rest(Handle& h, const ReasmFn& reasm, std::vector<int
   }
 }
 
+// Factorisation of the assembled batch (prepare + assembly already queued and
+// the handle's sizes set; the metadata read back wherever has_generic is set,
+// lu_mode is 0 or a summary was not taken).  Blocked problems: the no-pivot
+// LU, then partial pivoting for the problems it rejects (o.lu_mode 1), or
+// partial pivoting for all (o.lu_mode 0) — the partial-pivoting blocked LU up
+// to PIVOT_MAX, the generic LU above it (and for the ROUTE_GENERIC problems).
+// `spec` is queued right after the LU, before the host waits for the rejected
+// list: work that skips rejected problems (the solves of the fused call).
+// Deferred (o.may_defer, every problem on the no-pivot blocked route): the
+// caller finishes later (factor_dense_finish).
 template <class F>
-static void factor_blocked(Handle& h, F&& spec, double* w0, double* w1, const ReasmFn& reasm,
-                           const std::function<void()>* pre_copy = nullptr, bool* deferred = nullptr) {
-  auto np_of = [](const QPMeta& mm) { return (mm.nsys + 31) & ~31; };
+static Factored factor_blocked(Handle& h, const FactorOpts& o, F&& spec) {
   std::vector<int32_t> glist;   // problems for the generic LU
   if (h.has_generic)
     for (int64_t b = 0; b < h.batch; ++b) {
       const QPMeta& mm = h.meta_host[b];
       if (qp_route(mm.iterative, mm.nsys) == ROUTE_GENERIC) glist.push_back((int32_t)b);
     }
-  if (deferred) *deferred = false;
-  if (h.lu_mode == 1) {
+  if (o.lu_mode == 1) {
     {
       PhaseTimer pt(h, DOPT_PHASE_QP_LU);
-      qp_nopiv_factor(h, dinv_of(h), w0, w1);
+      qp_nopiv_factor(h, dinv_of(h), o.w0, o.w1);
     }
-    if (pre_copy) (*pre_copy)();   // kernels whose metadata the read-back below should carry (NLP: the pivot check)
-    if (h.blocked_npmax) meta_copy_side(h);
+    if (o.pre_readback) o.pre_readback();   // (NLP: the pivot check)
+    if (h.blocked_npmax) meta_readback(h);
     spec();
     h.n_pivot = 0;
-    if (deferred && h.blocked_npmax && glist.empty()) {   // the caller finishes later (factor_dense_finish)
-      *deferred = true;
-      return;
-    }
-    factor_blocked_rest(h, reasm, glist, true);
+    if (o.may_defer && h.blocked_npmax && glist.empty()) return Factored::Deferred;
+    factor_blocked_rest(h, o.reasm, glist, true);
   } else {
     {
       PhaseTimer pt(h, DOPT_PHASE_QP_LU_PIVOT);
@@ -970,35 +972,37 @@ static void factor_blocked(Handle& h, F&& spec, double* w0, double* w1, const Re
     if (h.blocked_npmax > PIVOT_MAX)
       for (int64_t b = 0; b < h.batch; ++b) {
         const QPMeta& mm = h.meta_host[b];
-        if (qp_route(mm.iterative, mm.nsys) == ROUTE_BLOCKED && np_of(mm) > PIVOT_MAX) glist.push_back((int32_t)b);
+        if (qp_route(mm.iterative, mm.nsys) == ROUTE_BLOCKED && padded32(mm.nsys) > PIVOT_MAX)
+          glist.push_back((int32_t)b);
       }
-    factor_blocked_rest(h, reasm, glist, false);
+    factor_blocked_rest(h, o.reasm, glist, false);
   }
+  return Factored::Done;
 }
 
-static ReasmFn qp_reasm(Handle& h) {
-  return [&h](const int32_t* pl, int count) { prep_assemble(h, pl, count); };
+// The QP's own options: the handle's LU mode, re-assembly by the prepare and
+// tile kernels.
+static FactorOpts qp_factor_opts(Handle& h) {
+  FactorOpts o;
+  o.lu_mode = h.lu_mode;
+  o.reasm = [&h](const int32_t* pl, int count) { prep_assemble(h, pl, count); };
+  return o;
 }
 
 void qp_factor(Handle& h) {
   if (!h.set) throw Error(-1, "dopt_qp_factor: dopt_qp_set has not been called");
   h.small_ready = false;   // K is overwritten
-  const bool summarised = prepare_batch(h);
-  meta_sizes(h, summarised);
-  factor_blocked(h, [] {}, nullptr, nullptr, qp_reasm(h));
+  BatchPrepareLaunch prep(h);
+  prep.wait_and_launch_tiles();
+  factor_blocked(h, qp_factor_opts(h), [] {});
   h.factored = true;
 }
 
-// The blocked factorisation of a batch already assembled into K / meta by a
-// caller (the NLP back-end), with `reasm` re-assembling the problems the
-// no-pivot LU rejects.  Sizes from h.blocked_npmax; blocked route only.
-void factor_dense(Handle& h, const ReasmFn& reasm, const std::function<void()>* pre_copy, bool* deferred) {
+Factored factor_dense(Handle& h, const FactorOpts& o) {
   h.has_generic = false;
   h.has_lsqr = false;
-  factor_blocked(h, [] {}, nullptr, nullptr, reasm, pre_copy, deferred);
+  return factor_blocked(h, o, [] {});
 }
-// The rest of a deferred factor_dense (no-pivot LU queued, its metadata
-// read-back in flight): the wait, then the rejected problems' fallbacks.
 void factor_dense_finish(Handle& h, const ReasmFn& reasm) {
   std::vector<int32_t> glist;
   factor_blocked_rest(h, reasm, glist, true);
@@ -1006,13 +1010,29 @@ void factor_dense_finish(Handle& h, const ReasmFn& reasm) {
 
 double* dense_dinv(Handle& h) { return dinv_of(h); }
 
-// LSQR (IterativeSolvers defaults) on the K slabs of the problems whose
-// meta.iterative is set: rhs / x stride nmax per problem (dopt_lhs_solve)
 void lsqr_slabs(Handle& h, int trans, const double* rhs, double* x) {
   h.lsqr_ws.ensure((size_t)h.batch * 5 * h.nmax * sizeof(double));
   hipLaunchKernelGGL(qp_lsqr_kernel, dim3((unsigned)h.batch), dim3(TPB), 0, h.stream, h.K.as<double>(),
                      h.meta.as<QPMeta>(), h.nmax, h.ld, trans, rhs, x, h.lsqr_ws.as<double>());
   check_launch();
+}
+
+// The generic LU's solves (when the last factorisation has any) and the LSQR
+// problems' (when the batch has any) of one direction: rhs / x stride nmax
+// per problem.  The blocked solves are launched by the callers.
+static void route_solves(Handle& h, int trans, const double* rhs, double* x) {
+  if (h.n_generic > 0) {
+    PhaseTimer pt(h, DOPT_PHASE_QP_SOLVE);
+    if ((size_t)h.nmax * sizeof(double) > 64 * 1024) throw Error(-1, "generic solve: system too large");
+    hipLaunchKernelGGL(qp_solve_kernel, dim3((unsigned)h.batch), dim3(TPB), (size_t)h.nmax * sizeof(double),
+                       h.stream, h.K.as<double>(), h.ipiv.as<int32_t>(), h.meta.as<QPMeta>(), h.nmax, h.ld, trans,
+                       rhs, x);
+    check_launch();
+  }
+  if (h.has_lsqr) {
+    PhaseTimer pt(h, DOPT_PHASE_QP_LSQR);
+    lsqr_slabs(h, trans, rhs, x);
+  }
 }
 
 // Per-direction work buffers (trans 0 = reverse, 1 = forward): reduced RHS,
@@ -1031,22 +1051,9 @@ static double* x_of(Handle& h, int trans) {
 static void finish_into(Handle& h, int trans, double* rhs, double* x, const double* full, double* out,
                         const double* pair_x = nullptr, double* pair_out = nullptr, bool solves_only = false) {
   const int B = (int)h.batch, n = h.n, m = h.m, p = h.p;
-  const int nmax = h.nmax, ld = h.ld;
+  const int nmax = h.nmax;
   QPMeta* meta = h.meta.as<QPMeta>();
-  if (h.n_generic > 0) {
-    PhaseTimer pt(h, DOPT_PHASE_QP_SOLVE);
-    if ((size_t)nmax * sizeof(double) > 64 * 1024) throw Error(-1, "generic solve: system too large");
-    hipLaunchKernelGGL(qp_solve_kernel, dim3(B), dim3(TPB), (size_t)nmax * sizeof(double), h.stream,
-                       h.K.as<double>(), h.ipiv.as<int32_t>(), meta, nmax, ld, trans, rhs, x);
-    check_launch();
-  }
-  if (h.has_lsqr) {
-    PhaseTimer pt(h, DOPT_PHASE_QP_LSQR);
-    h.lsqr_ws.ensure((size_t)B * 5 * nmax * sizeof(double));
-    hipLaunchKernelGGL(qp_lsqr_kernel, dim3(B), dim3(TPB), 0, h.stream, h.K.as<double>(), meta, nmax, ld,
-                       trans, rhs, x, h.lsqr_ws.as<double>());
-    check_launch();
-  }
+  route_solves(h, trans, rhs, x);
   if (solves_only) return;
   static const double dummy = 0.0;
   PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
@@ -1138,24 +1145,7 @@ void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, do
   }
   // generic / LSQR routes per seed, then every seed's outputs in one launch
   QPMeta* meta = h.meta.as<QPMeta>();
-  for (int j = 0; j < k; ++j) {
-    double* rhs = rk + j * blk;
-    double* x = xk + j * blk;
-    if (h.n_generic > 0) {
-      PhaseTimer pt(h, DOPT_PHASE_QP_SOLVE);
-      if ((size_t)nmax * sizeof(double) > 64 * 1024) throw Error(-1, "generic solve: system too large");
-      hipLaunchKernelGGL(qp_solve_kernel, dim3(B), dim3(TPB), (size_t)nmax * sizeof(double), h.stream,
-                         h.K.as<double>(), h.ipiv.as<int32_t>(), meta, nmax, h.ld, trans, rhs, x);
-      check_launch();
-    }
-    if (h.has_lsqr) {
-      PhaseTimer pt(h, DOPT_PHASE_QP_LSQR);
-      h.lsqr_ws.ensure((size_t)B * 5 * nmax * sizeof(double));
-      hipLaunchKernelGGL(qp_lsqr_kernel, dim3(B), dim3(TPB), 0, h.stream, h.K.as<double>(), meta, nmax, h.ld,
-                         trans, rhs, x, h.lsqr_ws.as<double>());
-      check_launch();
-    }
-  }
+  for (int j = 0; j < k; ++j) route_solves(h, trans, rk + j * blk, xk + j * blk);
   static const double dummy = 0.0;
   PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
   const int nck = (k + OKC - 1) / OKC;
@@ -1234,7 +1224,7 @@ void qp_forward_reverse(Handle& h, const double* dl_dz, const double* dQ,
                         double* out_fwd) {
   if (!h.set) throw Error(-1, "dopt_qp_forward_reverse: dopt_qp_set has not been called");
   const FwdTangents T = tangents(h, dQ, dq, dG, dh, dA, db);
-  const bool summarised = prepare_batch(h);
+  BatchPrepareLaunch prep(h);
   // no-pivot LU: both right-hand sides ride along as a bordering column / row
   // and come out forward-swept (w0, w1, written by the RHS kernels next to
   // rhs), leaving the solves the backward sweeps; rhs itself stays intact for
@@ -1248,7 +1238,7 @@ void qp_forward_reverse(Handle& h, const double* dl_dz, const double* dQ,
   }
   rev_rhs(h, dl_dz, w0);
   fwd_rhs(h, T, w1);
-  meta_sizes(h, summarised);
+  prep.wait_and_launch_tiles();
   if (!h.blocked_npmax) w0 = w1 = nullptr;
   auto solve2 = [&](int sel, const double* sw0, const double* sw1) {
     PhaseTimer pt(h, DOPT_PHASE_QP_SOLVE);
@@ -1259,13 +1249,13 @@ void qp_forward_reverse(Handle& h, const double* dl_dz, const double* dQ,
   // fallback (partial pivoting, the generic LU) recomputes them all after
   const bool spec_out = h.lu_mode == 1 && !h.has_generic && !h.has_lsqr;
   h.n_generic = 0;   // (the speculative outputs must not run the previous factorisation's generic solves)
-  factor_blocked(
-      h,
-      [&] {
-        solve2(h.lu_mode == 1 ? LU_SEL_NOPIV : LU_SEL_ALL, w0, w1);
-        if (spec_out) finish_pair(h, out_rev, out_fwd);
-      },
-      w0, w1, qp_reasm(h));
+  FactorOpts o = qp_factor_opts(h);
+  o.w0 = w0;
+  o.w1 = w1;
+  factor_blocked(h, o, [&] {
+    solve2(h.lu_mode == 1 ? LU_SEL_NOPIV : LU_SEL_ALL, w0, w1);
+    if (spec_out) finish_pair(h, out_rev, out_fwd);
+  });
   if (h.n_pivot > 0) solve2(LU_SEL_PIVOT, nullptr, nullptr);
   if (!spec_out || h.n_pivot > 0 || h.n_generic > 0) finish_pair(h, out_rev, out_fwd);
   h.factored = true;   // the factors stay valid for later reverse / forward calls

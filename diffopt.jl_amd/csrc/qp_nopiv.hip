@@ -145,7 +145,7 @@ constexpr int BSTR = NB64 * NB64 + NB64;
 
 __device__ __forceinline__ int nlu_np(const QPMeta& mm) {
   if (qp_route(mm.iterative, mm.nsys) != ROUTE_BLOCKED) return 0;
-  return (mm.nsys + 31) & ~31;
+  return padded32(mm.nsys);
 }
 
 // the growth bound of a problem (no bound when its max |K| is unknown: 0)
@@ -2335,7 +2335,7 @@ void qp_nopiv_factor(Handle& h, double* dinv, double* w0, double* w1) {
   const bool qp = h.kind == DOPT_KIND_QP;
   const double* kls = qp ? h.kls.as<double>() : nullptr;
   double* kamax = h.kamax.as<double>();
-  // (the count of the others: meta_sizes, from this call's metadata)
+  // (the count of the others: BatchPrepareLaunch, from this call's metadata)
   const int lower = qp && h.nonsym_blocked == 0 ? 1 : 0;
   // step 0 of the P-symmetric problems reads the QP inputs (no K assembly)
   static const double zero = 0.0;

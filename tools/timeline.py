@@ -5,6 +5,13 @@ kernel, the first launch of a QP step), with its start offset, duration and
 queue, so the critical chain across the engine's two streams can be read off.
 
   python tools/timeline.py DIR [first_kernel_substring] [steps_from_end]
+
+`--launches` instead lists every dispatch of the trace in the order the host
+issued it (dispatch id), without times: kernel, grid, workgroup, LDS bytes and
+stream (numbered by first appearance) — two builds that launch the same
+sequence give the same list, line for line.
+
+  python tools/timeline.py DIR --launches
 """
 import csv
 import glob
@@ -25,6 +32,16 @@ def short(name):
     m = re.search(r"(\w+(?:<[^>]*>)?)\(", name)
     return (m.group(1) if m else name)[:40]
 
+
+if "--launches" in sys.argv[2:]:
+    rows.sort(key=lambda r: int(r["Dispatch_Id"]))
+    seen = {}
+    for r in rows:
+        q = seen.setdefault(r.get("Stream_Id", r.get("Queue_Id", "?")), len(seen))
+        grid = "x".join(r.get(f"Grid_Size_{a}", "?") for a in "XYZ")
+        wg = "x".join(r.get(f"Workgroup_Size_{a}", "?") for a in "XYZ")
+        print(f"grid {grid:16s} wg {wg:10s} lds {r.get('LDS_Block_Size', '?'):>6s}  s{q}  {r['Kernel_Name']}")
+    sys.exit(0)
 
 starts = [i for i, r in enumerate(rows) if first in r["Kernel_Name"]]
 if len(starts) < back + 1:
