@@ -863,6 +863,58 @@ int dopt_qp_params_reverse_k(dopt_handle* h, int32_t k, const double* dl_dz, int
   });
 }
 
+// Reverse with seeds on the duals (params.hip; the sparse route: sparse.hip, one seed)
+int dopt_qp_reverse_duals_k(dopt_handle* h, int32_t k, const double* dl_dz, const double* dl_dlam,
+                            const double* dl_dnu, double* out) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_reverse_duals_k on a non-QP handle");
+    if (k < 1) throw Error(-1, "k must be positive");
+    if (h->sparse && k > 1) throw Error(-1, "multi-RHS calls need factors: not on the sparse (LSQR) route");
+    if (!out) throw Error(-1, "out is required");
+    if (!dl_dz && !dl_dlam && !dl_dnu) throw Error(-1, "dopt_qp_reverse_duals_k: at least one seed block is required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p;
+    int rc = 0;
+    staged_call(*h, k, {{dl_dz, 0, B * n}, {m ? dl_dlam : nullptr, 1, B * m}, {p ? dl_dnu : nullptr, 2, B * p}},
+                {{out, 0, B * L}}, [&](const double** i, double** o) {
+                  if (h->sparse) dopt::sp_reverse_duals(*h, i[0], i[1], i[2], o[0]);
+                  else dopt::qp_reverse_duals_k(*h, k, i[0], i[1], i[2], o[0]);
+                });
+    if (h->sparse) wait(*h);
+    else rc = first_info(*h);
+    h->last_time = tm.s();
+    return rc;
+  });
+}
+
+int dopt_qp_params_reverse_duals_k(dopt_handle* h, int32_t k, const double* dl_dz, const double* dl_dlam,
+                                   const double* dl_dnu, int32_t nparam, int64_t nterms, const int32_t* t_param,
+                                   const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var,
+                                   const double* t_coef, double* out_rev, double* out_dp) {
+  return guarded(h, [&]() {
+    if (h->kind != DOPT_KIND_QP) throw Error(-1, "dopt_qp_params_reverse_duals_k on a non-QP handle");
+    if (h->sparse) throw Error(-1, "multi-RHS calls need factors: not on the sparse (LSQR) route");
+    if (k < 1) throw Error(-1, "k must be positive");
+    if (!dl_dz && !dl_dlam && !dl_dnu)
+      throw Error(-1, "dopt_qp_params_reverse_duals_k: at least one seed block is required");
+    Timer tm;
+    const size_t B = h->batch, n = h->n, m = h->m, p = h->p, L = n + m + p, P = nparam > 0 ? (size_t)nparam : 0;
+    const bool work = P && B;
+    staged_call(*h, k,
+                {{work ? dl_dz : nullptr, 0, B * n},
+                 {work && m ? dl_dlam : nullptr, 1, B * m},
+                 {work && p ? dl_dnu : nullptr, 2, B * p}},
+                {{work ? out_rev : nullptr, 0, B * L}, {work ? out_dp : nullptr, 1, B * P}},
+                [&](const double** i, double** o) {
+                  dopt::qp_params_reverse_duals_k(*h, k, i[0], i[1], i[2], nparam, nterms, t_param, t_kind, t_index,
+                                                  t_var, t_coef, o[0], o[1]);
+                });
+    const int rc = work ? first_info(*h) : 0;
+    h->last_time = tm.s();
+    return rc;
+  });
+}
+
 int dopt_qp_forward_reverse(dopt_handle* h, const double* dl_dz, const double* dQ,
                             const double* dq, const double* dG, const double* dh,
                             const double* dA, const double* db, double* out_rev,

@@ -254,7 +254,7 @@ struct Handle {
   DevBuf qsy;                // Q symmetry check: max |Q|, |A| (B doubles), then the asymmetry flags (B int32)
   bool qsym_pending = false; // the check is queued on `aux`; the LU waits for ev_qsym first
   DevBuf fwdw;               // fused call: both right-hand sides, forward-swept inside the no-pivot LU
-  DevBuf krhs, kx, kfull;    // multi-RHS calls: k seeds' reduced RHS, solutions, full forward RHS
+  DevBuf krhs, kx, kfull;    // multi-RHS calls: k seeds' reduced RHS, solutions, full forward RHS (or full dual-seeded reverse RHS)
   DevBuf mws;                // multi-RHS: per-workgroup vectors of tall systems (qp_multi.hip)
   QPMeta* meta_host = nullptr;     // pinned copy of `meta` (asynchronous read-back)
   hipEvent_t meta_ev = nullptr;    // recorded after the read-back copy
@@ -484,8 +484,15 @@ void qp_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, 
 void qp_forward_k(Handle& h, int k, const double* dQ, const double* dq, const double* dG, const double* dh,
                   const double* dA, const double* db, double* out);
 // k right-hand sides already in rk (reduced; fk: the full forward copies, null for trans 0) through the multi-RHS
-// solve, the generic / LSQR routes per seed and qp_output_k_kernel (qp.hip); rk / xk / fk: seed-major, stride B·nmax
-void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out);
+// solve, the generic / LSQR routes per seed and qp_output_k_kernel (qp.hip); rk / xk / fk: seed-major, stride B·nmax.
+// seeded (trans 0 only): fk holds the full-length seeds [g_z; g_λ; g_ν], whose g_λ the eliminated rows' recovery reads
+void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out, bool seeded = false);
+// reverse with seeds on the duals too (params.hip): −LHS⁻¹·[g_z; g_λ; g_ν] per seed; any seed pointer may be null (zero)
+void qp_reverse_duals_k(Handle& h, int k, const double* g_z, const double* g_lam, const double* g_nu, double* out);
+void qp_params_reverse_duals_k(Handle& h, int k, const double* g_z, const double* g_lam, const double* g_nu,
+                               int nparam, int64_t nterms, const int32_t* t_param, const int32_t* t_kind,
+                               const int32_t* t_index, const int32_t* t_var, const double* t_coef, double* out_rev,
+                               double* out_dp);
 // QP parameter calls on k seeds (params.hip): right-hand sides straight from the term table, then solve_k
 void qp_params_forward_k(Handle& h, int k, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,
                          const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
@@ -559,6 +566,8 @@ void sp_forward_reverse_csc(Handle& h, const double* dl_dz, const CscArg* T, con
 // own G / A), out[k] = the values per entry (nullptr: skipped)
 void sp_reverse_grads_at(Handle& h, const double* rev, const CscArg* P, double* const* out, int* err);
 void sp_reverse(Handle& h, const double* dl_dz, double* out);
+// ... with seeds on the duals: −LHS⁻¹·[g_z; g_λ; g_ν] (any pointer may be null: zero)
+void sp_reverse_duals(Handle& h, const double* g_z, const double* g_lam, const double* g_nu, double* out);
 void sp_forward(Handle& h, const FwdTangents& T, double* out);
 void sp_forward_reverse(Handle& h, const double* dl_dz, const FwdTangents& T, double* out_rev, double* out_fwd);
 void nlp_configure(Handle& h);

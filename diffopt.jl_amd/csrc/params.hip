@@ -198,6 +198,41 @@ __global__ __launch_bounds__(PTPB) void qp_poi_rev_rhs_kernel(const double* __re
   }
 }
 
+// Reverse right-hand sides of a chunk of seeds with a loss gradient on the
+// duals too: [g_z; g_λ; g_ν] of the column (a null block is zero).  The
+// full-length copy (`full`, rows [0, nmax): zeros past n+m+p) is what the
+// output kernel reads an eliminated row's g_λ from; the reduced copy (`rhs`)
+// goes through rpos and meta.nk as qp_fwd_rhs_kernel (qp.hip) scatters its
+// rows, and only its entries < nsys are written, as qp_rev_rhs_kernel does.
+__global__ __launch_bounds__(PTPB) void qp_rev_rhs_duals_kernel(
+    const double* __restrict__ g_z, const double* __restrict__ g_lam, const double* __restrict__ g_nu, int n, int m,
+    int p, int nmax, int B, int64_t cols, const int32_t* __restrict__ rpos, const QPMeta* __restrict__ meta,
+    double* __restrict__ full, double* __restrict__ rhs) {
+  const int r = blockIdx.x * PTPB + threadIdx.x;
+  if (r >= nmax) return;
+  const int L = n + m + p;
+  for (int64_t c = blockIdx.y; c < cols; c += gridDim.y) {
+    const int b = (int)(c % B);
+    double v = 0.0;
+    int dst = -1;   // the entry's place in the reduced system (−1: an eliminated row, or padding)
+    if (r < n) {
+      if (g_z) v = g_z[(size_t)c * n + r];
+      dst = r;
+    } else if (r < n + m) {
+      const int l = r - n;
+      if (g_lam) v = g_lam[(size_t)c * m + l];
+      const int kk = rpos[(size_t)b * m + l];
+      if (kk >= 0) dst = n + kk;
+    } else if (r < L) {
+      const int e = r - n - m;
+      if (g_nu) v = g_nu[(size_t)c * p + e];
+      dst = n + meta[b].nk + e;
+    }
+    full[(size_t)c * nmax + r] = v;
+    if (dst >= 0) rhs[(size_t)c * nmax + dst] = v;   // dst < nsys: no two threads share an entry
+  }
+}
+
 // Reverse accumulation over the columns (parameters.jl:341-534): one thread
 // per (column, parameter), out[c·nparam + r] = Σ_t c_t·s_t over the
 // parameter's terms in the caller's order, from the column's full reverse
@@ -650,6 +685,82 @@ void qp_params_forward_k(Handle& h, int k, const double* dp, int nparam, int64_t
   DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `cr` / `cv` are done
 }
 
+namespace {
+
+// The seeds of a reverse call on k columns.  duals: the loss gradient has λ /
+// ν blocks (a null pointer is a zero block) and the right-hand sides are
+// qp_rev_rhs_duals_kernel's; otherwise [dl_dz; 0] or the unit seeds
+// (qp_poi_rev_rhs_kernel).
+struct RevSeeds {
+  const double* z;
+  const double* lam;
+  const double* nu;
+  bool duals;
+};
+
+// The chunk loop of the reverse `_k` calls on kept factors: per chunk of
+// qp_jacobian_chunk seeds the right-hand sides, solve_k into the chunk's place
+// in out_rev (null: the handle's scratch, overwritten by the next chunk), then
+// after(s0, cols, rev) on the chunk's outputs.
+template <class After>
+void qp_reverse_chunks(Handle& h, int k, const RevSeeds& g, double* out_rev, After&& after) {
+  const int n = h.n, m = h.m, p = h.p, nmax = h.nmax;
+  const size_t B = h.batch, L = (size_t)n + m + p, blk = B * nmax;
+  const int chunk = qp_jacobian_chunk(h, k);
+  h.krhs.ensure((size_t)chunk * blk * sizeof(double));
+  h.kx.ensure((size_t)chunk * blk * sizeof(double));
+  if (g.duals) h.kfull.ensure((size_t)chunk * blk * sizeof(double));
+  if (!out_rev) h.qjac.ensure((size_t)chunk * B * L * sizeof(double));
+  double* rk = h.krhs.as<double>();
+  double* xk = h.kx.as<double>();
+  double* fk = g.duals ? h.kfull.as<double>() : nullptr;
+  for (int s0 = 0; s0 < k; s0 += chunk) {
+    const int kc = std::min(chunk, k - s0);
+    const int64_t cols = (int64_t)kc * (int64_t)B;
+    auto at = [&](const double* a, int len) { return a ? a + (size_t)s0 * B * len : nullptr; };
+    {
+      PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
+      if (g.duals)
+        hipLaunchKernelGGL(qp_rev_rhs_duals_kernel, poi_grid(nmax, cols), dim3(PTPB), 0, h.stream, at(g.z, n),
+                           m ? at(g.lam, m) : nullptr, p ? at(g.nu, p) : nullptr, n, m, p, nmax, (int)B, cols,
+                           qp_rpos(h), h.meta.as<QPMeta>(), fk, rk);
+      else
+        hipLaunchKernelGGL(qp_poi_rev_rhs_kernel, poi_grid(nmax, cols), dim3(PTPB), 0, h.stream, at(g.z, n), s0, n,
+                           nmax, (int)B, cols, rk);
+      DOPT_CHECK_HIP(hipGetLastError());
+    }
+    double* rev = out_rev ? out_rev + (size_t)s0 * B * L : h.qjac.as<double>();
+    solve_k(h, 0, kc, rk, xk, fk, rev, g.duals);
+    after(s0, cols, rev);
+  }
+}
+
+// The parameter gradients of the reverse `_k` calls: the term table by
+// parameter, then qp_poi_reverse_k_kernel over every chunk's reverse outputs.
+void qp_params_reverse_chunks(Handle& h, int k, const RevSeeds& g, int nparam, int64_t nterms, const int32_t* t_param,
+                              const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var,
+                              const double* t_coef, double* out_rev, double* out_dp) {
+  const int n = h.n, m = h.m, p = h.p;
+  const size_t B = h.batch;
+  std::vector<int32_t> var(nterms, 0);
+  for (int64_t t = 0; t < nterms; ++t)
+    if (t_kind[t] == 4 || t_kind[t] == 5) var[t] = t_var[t];
+  const Csr c = csr_by(nparam, nterms, std::vector<int32_t>(t_param, t_param + nterms), t_param, t_kind, t_index,
+                       t_coef, var.data());
+  DevCsr d(h, c);
+  static const double dummy = 0.0;
+  qp_reverse_chunks(h, k, g, out_rev, [&](int s0, int64_t cols, const double* rev) {
+    PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
+    hipLaunchKernelGGL(qp_poi_reverse_k_kernel, poi_grid(nparam, cols), dim3(PTPB), 0, h.stream, rev, h.z,
+                       m ? h.lam : &dummy, p ? h.nu : &dummy, n, m, p, (int)B, cols, nparam, d.ptr, d.kind, d.index,
+                       d.var, d.coef, out_dp + (size_t)s0 * B * nparam);
+    DOPT_CHECK_HIP(hipGetLastError());
+  });
+  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
+}
+
+}  // namespace
+
 void qp_params_reverse_k(Handle& h, int k, const double* dl_dz, int nparam, int64_t nterms, const int32_t* t_param,
                          const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var, const double* t_coef,
                          double* out_rev, double* out_dp) {
@@ -659,39 +770,34 @@ void qp_params_reverse_k(Handle& h, int k, const double* dl_dz, int nparam, int6
   if (nparam == 0 || k == 0 || h.batch == 0) return;
   if (!out_dp) throw Error(-1, "dopt_qp_params_reverse_k: out_dp is required");
   if (!h.factored) qp_factor(h);
-  const int n = h.n, m = h.m, p = h.p, nmax = h.nmax;
-  const size_t B = h.batch, L = (size_t)n + m + p, blk = B * nmax;
-  std::vector<int32_t> var(nterms, 0);
-  for (int64_t t = 0; t < nterms; ++t)
-    if (t_kind[t] == 4 || t_kind[t] == 5) var[t] = t_var[t];
-  const Csr c = csr_by(nparam, nterms, std::vector<int32_t>(t_param, t_param + nterms), t_param, t_kind, t_index,
-                       t_coef, var.data());
-  DevCsr d(h, c);
-  const int chunk = qp_jacobian_chunk(h, k);
-  h.krhs.ensure((size_t)chunk * blk * sizeof(double));
-  h.kx.ensure((size_t)chunk * blk * sizeof(double));
-  if (!out_rev) h.qjac.ensure((size_t)chunk * B * L * sizeof(double));
-  double* rk = h.krhs.as<double>();
-  double* xk = h.kx.as<double>();
-  static const double dummy = 0.0;
-  for (int s0 = 0; s0 < k; s0 += chunk) {
-    const int kc = std::min(chunk, k - s0);
-    const int64_t cols = (int64_t)kc * (int64_t)B;
-    {
-      PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
-      hipLaunchKernelGGL(qp_poi_rev_rhs_kernel, poi_grid(nmax, cols), dim3(PTPB), 0, h.stream,
-                         dl_dz ? dl_dz + (size_t)s0 * B * n : nullptr, s0, n, nmax, (int)B, cols, rk);
-      DOPT_CHECK_HIP(hipGetLastError());
-    }
-    double* rev = out_rev ? out_rev + (size_t)s0 * B * L : h.qjac.as<double>();
-    solve_k(h, 0, kc, rk, xk, nullptr, rev);
-    PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
-    hipLaunchKernelGGL(qp_poi_reverse_k_kernel, poi_grid(nparam, cols), dim3(PTPB), 0, h.stream, rev, h.z,
-                       m ? h.lam : &dummy, p ? h.nu : &dummy, n, m, p, (int)B, cols, nparam, d.ptr, d.kind, d.index,
-                       d.var, d.coef, out_dp + (size_t)s0 * B * nparam);
-    DOPT_CHECK_HIP(hipGetLastError());
-  }
-  DOPT_CHECK_HIP(hipStreamSynchronize(h.stream));   // the copies out of `c` are done
+  qp_params_reverse_chunks(h, k, RevSeeds{dl_dz, nullptr, nullptr, false}, nparam, nterms, t_param, t_kind, t_index,
+                           t_var, t_coef, out_rev, out_dp);
+}
+
+// Reverse with a loss gradient on the duals as well: −LHS⁻¹·[g_z; g_λ; g_ν]
+// per seed (seeds with respect to the engine's λ and ν).  Every k goes through
+// solve_k, so a seed's result does not depend on how the seeds are grouped.
+void qp_reverse_duals_k(Handle& h, int k, const double* g_z, const double* g_lam, const double* g_nu, double* out) {
+  qp_k_checks(h, "dopt_qp_reverse_duals_k");
+  if (k < 1) throw Error(-1, "dopt_qp_reverse_duals_k: k must be positive");
+  if (!out) throw Error(-1, "dopt_qp_reverse_duals_k: out is required");
+  if (h.batch == 0) return;
+  if (!h.factored) qp_factor(h);   // (also a handle that has only run the one-launch small path)
+  qp_reverse_chunks(h, k, RevSeeds{g_z, g_lam, g_nu, true}, out, [](int, int64_t, const double*) {});
+}
+
+void qp_params_reverse_duals_k(Handle& h, int k, const double* g_z, const double* g_lam, const double* g_nu,
+                               int nparam, int64_t nterms, const int32_t* t_param, const int32_t* t_kind,
+                               const int32_t* t_index, const int32_t* t_var, const double* t_coef, double* out_rev,
+                               double* out_dp) {
+  qp_k_checks(h, "dopt_qp_params_reverse_duals_k");
+  if (k < 1) throw Error(-1, "dopt_qp_params_reverse_duals_k: k must be positive");
+  validate(h, nparam, nterms, t_param, t_kind, t_index, t_coef, t_var, true);
+  if (nparam == 0 || h.batch == 0) return;
+  if (!out_dp) throw Error(-1, "dopt_qp_params_reverse_duals_k: out_dp is required");
+  if (!h.factored) qp_factor(h);
+  qp_params_reverse_chunks(h, k, RevSeeds{g_z, g_lam, g_nu, true}, nparam, nterms, t_param, t_kind, t_index, t_var,
+                           t_coef, out_rev, out_dp);
 }
 
 void conic_params_forward(Handle& h, const double* dp, int nparam, int64_t nterms, const int32_t* t_param,

@@ -475,7 +475,12 @@ __global__ __launch_bounds__(TPB) void qp_output_kernel(
 // eliminated rows read their G row once per OKC seeds instead of once per
 // seed; each seed's arithmetic (and summation order) is qp_output_kernel's.
 // Seed j of problem b: x / full at + (j·B + b)·nmax, out at + (j·B + b)·(n+m+p).
+// SEEDED (reverse with a loss gradient on the duals, dopt_qp_reverse_duals_k):
+// row n+l of LHS then reads G_l·x_z + s_l·x_λl = g_λl, so an eliminated row
+// recovers as x_λl = (g_λl − G_l·x_z)/s_l with g_λl from the full copy `full`;
+// the unseeded expression keeps its literal 0.0.
 constexpr int OKC = 16;
+template <bool SEEDED>
 __global__ __launch_bounds__(TPB) void qp_output_k_kernel(
     const double* __restrict__ x, const double* __restrict__ G, const double* __restrict__ s,
     const int32_t* __restrict__ rpos, const QPMeta* __restrict__ meta, const double* __restrict__ full,
@@ -522,8 +527,13 @@ __global__ __launch_bounds__(TPB) void qp_output_k_kernel(
       }
     }
 #pragma unroll
-    for (int c = 0; c < OKC; ++c)
-      if (c < kc) out[((size_t)(j0 + c) * B + b) * L + n + l] = -((0.0 - acc[c]) / sl);
+    for (int c = 0; c < OKC; ++c) {
+      if (c < kc) {
+        const size_t pj = (size_t)(j0 + c) * B + b;
+        if (SEEDED) out[pj * L + n + l] = -((full[pj * nmax + n + l] - acc[c]) / sl);
+        else out[pj * L + n + l] = -((0.0 - acc[c]) / sl);
+      }
+    }
   }
 }
 
@@ -1136,7 +1146,7 @@ void qp_forward(Handle& h, const double* dQ, const double* dq, const double* dG,
 // multi-RHS row): seed j's inputs and outputs are standard batch blocks at
 // offset j·B·len; the blocked problems' k solves run in one launch
 // (qp_multi.hip), the other routes and the outputs per seed.
-void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out) {
+void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, double* out, bool seeded) {
   const size_t blk = (size_t)h.batch * h.nmax;
   const int B = (int)h.batch, n = h.n, m = h.m, p = h.p, nmax = h.nmax;
   {
@@ -1150,8 +1160,12 @@ void solve_k(Handle& h, int trans, int k, double* rk, double* xk, double* fk, do
   PhaseTimer pt(h, DOPT_PHASE_QP_OUTPUT);
   const int nck = (k + OKC - 1) / OKC;
   const size_t lds = (!trans && (size_t)n * OKC * 8 <= 48 * 1024) ? (size_t)n * OKC * 8 : 0;
-  hipLaunchKernelGGL(qp_output_k_kernel, dim3(B, nck), dim3(TPB), lds, h.stream, xk, m ? h.G : &dummy,
-                     h.s.as<double>(), rpos_of(h), meta, fk ? fk : xk, B, k, n, m, p, nmax, trans, out);
+  auto go = [&](auto kern) {
+    hipLaunchKernelGGL(kern, dim3(B, nck), dim3(TPB), lds, h.stream, xk, m ? h.G : &dummy, h.s.as<double>(),
+                       rpos_of(h), meta, fk ? fk : xk, B, k, n, m, p, nmax, trans, out);
+  };
+  if (seeded) go(qp_output_k_kernel<true>);   // reverse with dual seeds: fk holds [g_z; g_λ; g_ν]
+  else go(qp_output_k_kernel<false>);
   check_launch();
 }
 

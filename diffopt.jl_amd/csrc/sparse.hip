@@ -176,6 +176,29 @@ __global__ __launch_bounds__(SP_SETUP) void sp_rev_rhs_kernel(const double* __re
   }
 }
 
+// reverse with seeds on the duals: [g_z; g_λ; g_ν] (a null block is zero); the
+// route eliminates nothing, so the full-length vector is the right-hand side
+__global__ __launch_bounds__(SP_SETUP) void sp_rev_rhs_duals_kernel(const double* __restrict__ g_z,
+                                                                    const double* __restrict__ g_lam,
+                                                                    const double* __restrict__ g_nu, int n, int m,
+                                                                    int p, int B, double* __restrict__ rhs) {
+  const int L = n + m + p;
+  const int64_t tot = (int64_t)B * L;
+  for (int64_t e = (int64_t)blockIdx.x * blockDim.x + threadIdx.x; e < tot; e += (int64_t)gridDim.x * blockDim.x) {
+    const int64_t b = e / L;
+    const int i = (int)(e - b * L);
+    double v = 0.0;
+    if (i < n) {
+      if (g_z) v = g_z[b * n + i];
+    } else if (i < n + m) {
+      if (g_lam) v = g_lam[b * m + (i - n)];
+    } else if (g_nu) {
+      v = g_nu[b * p + (i - n - m)];
+    }
+    rhs[e] = v;
+  }
+}
+
 // forward: [dQ z + dq + dGᵀλ + dAᵀν; λ∘(dG z) − λ∘dh; dA z − db] from the dense
 // column-major tangents of the ABI (null = zero); one workgroup per problem,
 // the z block by one thread per entry j (column j of dG / dA is contiguous:
@@ -705,6 +728,19 @@ void sp_reverse(Handle& h, const double* dl_dz, double* out) {
   if (!h.factored) sp_factor(h);
   double* r = sp_rhs(h, 0);
   sp_rev_rhs(h, dl_dz, r);
+  sp_lsqr(h, 1, 0, 0, r, r, out, out);
+}
+
+void sp_reverse_duals(Handle& h, const double* g_z, const double* g_lam, const double* g_nu, double* out) {
+  if (!h.factored) sp_factor(h);
+  double* r = sp_rhs(h, 0);
+  {
+    const int B = (int)h.batch, L = h.n + h.m + h.p;
+    PhaseTimer pt(h, DOPT_PHASE_QP_RHS);
+    hipLaunchKernelGGL(sp_rev_rhs_duals_kernel, dim3(grid1((int64_t)B * L, SP_SETUP)), dim3(SP_SETUP), 0, h.stream,
+                       g_z, h.m ? g_lam : nullptr, h.p ? g_nu : nullptr, h.n, h.m, h.p, B, r);
+    DOPT_CHECK_HIP(hipGetLastError());
+  }
   sp_lsqr(h, 1, 0, 0, r, r, out, out);
 }
 

@@ -87,6 +87,9 @@ SIGNATURES = {
                                  + [ctypes.c_void_p] * 6),
     "dopt_qp_params_reverse_k": (ctypes.c_int, [_h, ctypes.c_int32, ctypes.c_void_p, ctypes.c_int32, ctypes.c_int64]
                                  + [ctypes.c_void_p] * 7),
+    "dopt_qp_reverse_duals_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 4),
+    "dopt_qp_params_reverse_duals_k": (ctypes.c_int, [_h, ctypes.c_int32] + [ctypes.c_void_p] * 3
+                                       + [ctypes.c_int32, ctypes.c_int64] + [ctypes.c_void_p] * 7),
     "dopt_conic_set": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 6 + [ctypes.c_void_p, ctypes.c_int32]),
     "dopt_conic_factor": (ctypes.c_int, [_h]),
     "dopt_conic_forward": (ctypes.c_int, [_h] + [ctypes.c_void_p] * 5),

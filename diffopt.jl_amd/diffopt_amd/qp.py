@@ -226,6 +226,38 @@ class QPBatch:
         _lib.check(rc, self.h, singular_ok)
         return out
 
+    def _dual_seeds(self, k, dl_dz, dl_dlam, dl_dnu):
+        """The three seed blocks of a `_duals` call as the ABI takes them
+        ((k·B, ·) vectors; None = zero, and for a block the model lacks)."""
+        kb = k * self.batch
+        st = self._stage([dl_dz, dl_dlam, dl_dnu])
+        seeds = [vector(dl_dz, (kb, self.n)) if dl_dz is not None else None,
+                 vector(dl_dlam, (kb, self.m)) if (dl_dlam is not None and self.m) else None,
+                 vector(dl_dnu, (kb, self.p)) if (dl_dnu is not None and self.p) else None]
+        return st, seeds
+
+    def reverse_duals_k(self, dl_dz=None, dl_dlam=None, dl_dnu=None, singular_ok=False):
+        """``reverse_k`` for a loss on the duals too (dopt_qp_reverse_duals_k):
+        seeds (k, B, n) / (k, B, m) / (k, B, p), None = zero, with respect to
+        the engine's λ and ν (OptNet sign: minus the MOI duals) →
+        (k, B, n+m+p) = −LHS⁻¹·[dl/dz; dl/dλ; dl/dν] per seed.  The output feeds
+        the same getters as ``reverse``'s.  A sparse-route handle takes k = 1."""
+        given = [a for a in (dl_dz, dl_dlam, dl_dnu) if a is not None]
+        if not given:
+            raise ValueError("reverse_duals needs at least one seed block")
+        k = int(given[0].shape[0])
+        st, seeds = self._dual_seeds(k, dl_dz, dl_dlam, dl_dnu)
+        out = Staged.empty((k, self.batch, self.L), st.mem == _lib.DOPT_MEM_DEVICE)
+        rc = self.lib.dopt_qp_reverse_duals_k(self.h, k, *[st.ptr(a) for a in seeds], st.ptr(out))
+        _lib.check(rc, self.h, singular_ok)
+        return out
+
+    def reverse_duals(self, dl_dz=None, dl_dlam=None, dl_dnu=None, singular_ok=False):
+        """One seed per problem (``reverse_duals_k`` with k = 1): seeds (B, n) /
+        (B, m) / (B, p) → (B, n+m+p)."""
+        one = [None if a is None else a[None] for a in (dl_dz, dl_dlam, dl_dnu)]
+        return self.reverse_duals_k(*one, singular_ok=singular_ok)[0]
+
     def forward_k(self, dQ=None, dq=None, dG=None, dh=None, dA=None, db=None, singular_ok=False):
         """k tangents per problem (dopt_qp_forward_k): each given tangent has a
         leading seed axis (k, B, …) → (k, B, n+m+p)."""
@@ -363,6 +395,25 @@ class QPBatch:
         pp = Staged.ptr
         rc = self.lib.dopt_qp_params_reverse_k(self.h, k, st.ptr(d), nparam, nt, pp(par), pp(kind), pp(idx),
                                                pp(var), pp(coef), st.ptr(rev), st.ptr(out))
+        _lib.check(rc, self.h, singular_ok)
+        return (out, rev) if want_rev else out
+
+    def params_reverse_duals_k(self, dl_dz, dl_dlam, dl_dnu, terms, nparam, want_rev=False, singular_ok=False):
+        """``params_reverse_k`` with seeds on the duals too
+        (dopt_qp_params_reverse_duals_k): seeds as ``reverse_duals_k``'s →
+        out_dp (k, B, nparam), or (out_dp, rev (k, B, n+m+p)) with ``want_rev``."""
+        given = [a for a in (dl_dz, dl_dlam, dl_dnu) if a is not None]
+        if not given:
+            raise ValueError("params_reverse_duals_k needs at least one seed block")
+        k, B, nparam = int(given[0].shape[0]), self.batch, int(nparam)
+        nt, par, kind, idx, var, coef = self._terms(terms, True)
+        st, seeds = self._dual_seeds(k, dl_dz, dl_dlam, dl_dnu)
+        dev = st.mem == _lib.DOPT_MEM_DEVICE
+        out = Staged.empty((k, B, nparam), dev)
+        rev = Staged.empty((k, B, self.L), dev) if want_rev else None
+        pp = Staged.ptr
+        rc = self.lib.dopt_qp_params_reverse_duals_k(self.h, k, *[st.ptr(a) for a in seeds], nparam, nt, pp(par),
+                                                     pp(kind), pp(idx), pp(var), pp(coef), st.ptr(rev), st.ptr(out))
         _lib.check(rc, self.h, singular_ok)
         return (out, rev) if want_rev else out
 
@@ -690,6 +741,7 @@ class Model:
         self.back_grad_cache = None
         self.diff_time = float("nan")
         self.input_dx = {}
+        self.input_dy = {LE: {}, EQ: {}}   # ReverseConstraintDual: row -> seed on the engine's λ / ν
         self.input_objective = None      # (dQ, dq)
         self.input_le = {}               # row -> (coeffs, constant)
         self.input_eq = {}
@@ -738,6 +790,16 @@ class Model:
     def set_reverse_variable_primal(self, i, value):
         self.input_dx[int(i)] = float(value)
 
+    def set_reverse_constraint_dual(self, kind, row, value):
+        """``ReverseConstraintDual`` of row ``row`` (moi_wrapper.jl:532-533): the
+        loss gradient with respect to the MOI ``ConstraintDual``, stored with
+        the OptNet sign flip of ``set_constraint_dual_start``.  The reference's
+        QP back-end ignores the attribute; here ``reverse_differentiate`` solves
+        with it (QPBatch.reverse_duals_k)."""
+        if kind not in (LE, EQ):
+            raise ValueError(kind)
+        self.input_dy[kind][int(row)] = -float(value)
+
     def set_forward_objective_function(self, dQ=None, dq=None):
         self.input_objective = (dQ, dq)
 
@@ -756,6 +818,7 @@ class Model:
 
     def empty_input_sensitivities(self):
         self.input_dx = {}
+        self.input_dy = {LE: {}, EQ: {}}
         self.input_objective = None
         self.input_le = {}
         self.input_eq = {}
@@ -783,7 +846,21 @@ class Model:
         dl = np.zeros(self.n)
         for i, v in self.input_dx.items():
             dl[i] = v
-        if self.nparam:   # the parameters' ReverseConstraintSet beside the getters (parameters.jl:341-534)
+        if self.input_dy[LE] or self.input_dy[EQ]:   # a loss on the duals too: the seeded solves
+            gl, gn = np.zeros(self.G.shape[0]), np.zeros(self.A.shape[0])
+            for i, v in self.input_dy[LE].items():
+                gl[i] = v
+            for i, v in self.input_dy[EQ].items():
+                gn[i] = v
+            seeds = (dl[None, None], gl[None, None], gn[None, None])
+            if self.nparam:
+                dp, rev = e.params_reverse_duals_k(*seeds, self.param_terms, self.nparam, want_rev=True)
+                self.back_param_cache = np.asarray(dp)[0, 0]
+            else:
+                rev = e.reverse_duals_k(*seeds)
+                self.back_param_cache = None
+            out = np.asarray(rev)[0, 0]
+        elif self.nparam:   # the parameters' ReverseConstraintSet beside the getters (parameters.jl:341-534)
             dp, rev = e.params_reverse_k(dl[None, None], self.param_terms, self.nparam, want_rev=True)
             out = np.asarray(rev)[0, 0]
             self.back_param_cache = np.asarray(dp)[0, 0]
@@ -831,6 +908,15 @@ class Model:
     def forward_variable_primal(self, i):
         """``ForwardVariablePrimal`` (:299-305)."""
         return self.forw_grad_cache[0][i]
+
+    def forward_constraint_dual(self, kind, row):
+        """``ForwardConstraintDual``: the tangent of the MOI ``ConstraintDual`` of
+        row ``row`` (minus the engine's dλ / dν)."""
+        if kind == LE:
+            return -self.forw_grad_cache[1][row]
+        if kind == EQ:
+            return -self.forw_grad_cache[2][row]
+        raise ValueError(kind)
 
     def reverse_objective_function(self):
         """``ReverseObjectiveFunction`` (:448-458): (dq, dQ) with

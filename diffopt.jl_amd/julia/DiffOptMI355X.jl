@@ -17,7 +17,8 @@
 # NonLinearKKTJacobianFactorization plug point) and `NLPBatch` (the batched
 # sensitivity surface).  Not exercised in CI: the build image has no Julia
 # (SURVEY.md §8(c)); the C-ABI it binds is exercised by the Python ctypes
-# harness.
+# harness.  That holds for the `dual_seeds` path of QPModel too: its
+# dopt_qp_reverse_duals_k call is tested through ctypes only.
 module DiffOptMI355X
 
 import DiffOpt
@@ -75,11 +76,17 @@ mutable struct QPModel <: DiffOpt.AbstractModel
     handle::Union{Nothing,Handle}
     device::Int
     staged::Any                          # (Q, G, h, A, x, λ, ν) the handle holds, or nothing
+    dual_seeds::Bool                     # reverse mode reads ReverseConstraintDual (input_cache.dy)
 end
 
-function QPModel(; device::Integer = 0)
+# `dual_seeds = false` is the reference's behaviour: its QP back-end ignores
+# ReverseConstraintDual (QuadraticProgram.jl:329 solves with [dl_dz; 0; 0]).
+# With `dual_seeds = true` and a non-empty input_cache.dy, reverse_differentiate!
+# solves −LHS⁻¹·[dl_dz; dl_dλ; dl_dν] (dopt_qp_reverse_duals_k); the getters are
+# the reference's, unchanged.
+function QPModel(; device::Integer = 0, dual_seeds::Bool = false)
     inner = QP.Model()
-    return QPModel(inner, inner.model, inner.input_cache, inner.x, nothing, device, nothing)
+    return QPModel(inner, inner.model, inner.input_cache, inner.x, nothing, device, nothing, dual_seeds)
 end
 
 MOI.is_empty(m::QPModel) = MOI.is_empty(m.inner)
@@ -166,8 +173,26 @@ function DiffOpt.reverse_differentiate!(m::QPModel)
             dl_dz[vi.value] = value
         end
         out = Vector{Float64}(undef, n + mi + p)
-        _check(ccall((:dopt_qp_reverse, LIB), Cint,
-                     (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h.ptr, dl_dz, out), h.ptr)
+        if m.dual_seeds && !isempty(m.input_cache.dy)
+            # dy holds MOI duals' seeds; the engine's λ, ν are minus the MOI
+            # duals (the ConstraintDualStart setters above), so the seeds flip too
+            dl_dlam, dl_dnu = zeros(mi), zeros(p)
+            for (ci, value) in m.input_cache.dy
+                if ci isa QP.LE
+                    dl_dlam[MOI.Utilities.rows(QP._inequalities(inner), ci)] = -value
+                elseif ci isa QP.EQ
+                    dl_dnu[MOI.Utilities.rows(QP._equalities(inner), ci)] = -value
+                end
+            end
+            GC.@preserve dl_dz dl_dlam dl_dnu out begin
+                _check(ccall((:dopt_qp_reverse_duals_k, LIB), Cint,
+                             (Ptr{Cvoid}, Int32, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}, Ptr{Float64}),
+                             h.ptr, Int32(1), dl_dz, _ptr(dl_dlam), _ptr(dl_dnu), out), h.ptr)
+            end
+        else
+            _check(ccall((:dopt_qp_reverse, LIB), Cint,
+                         (Ptr{Cvoid}, Ptr{Float64}, Ptr{Float64}), h.ptr, dl_dz, out), h.ptr)
+        end
         inner.back_grad_cache = _split(out, n, mi)
     end
     return

@@ -334,6 +334,38 @@ int dopt_qp_params_forward_k(dopt_handle* h, int32_t k, const double* dp, int32_
 int dopt_qp_params_reverse_k(dopt_handle* h, int32_t k, const double* dl_dz, int32_t nparam, int64_t nterms,
                              const int32_t* t_param, const int32_t* t_kind, const int32_t* t_index,
                              const int32_t* t_var, const double* t_coef, double* out_rev, double* out_dp);
+/* Reverse mode with a loss gradient on the duals as well: for a loss
+ * l(z, λ, ν), per seed and problem
+ *   [dz; dλ; dν] = −LHS⁻¹ · [dl/dz; dl/dλ; dl/dν]
+ * with LHS = [Q, GᵀD(λ), Aᵀ; G, D(Gz−h), 0; A, 0, 0] as dopt_qp_reverse solves
+ * it with [dl/dz; 0; 0]; an eliminated inequality row (λ_i == 0, s_i ≠ 0)
+ * recovers as x_λi = (dl/dλ_i − G_i·x_z)/s_i.  The output feeds the same
+ * getters (dopt_qp_reverse_grads, dopt_qp_params_reverse): dq = dz, g_const_i =
+ * λ_i·dλ_i, …  Sign convention: the seeds are with respect to the engine's λ
+ * and ν (the OptNet sign dopt_qp_set takes), which are minus the MOI duals — a
+ * caller holding dl/d(MOI dual) passes its negative.  The reference's QP
+ * back-end ignores ReverseConstraintDual (QuadraticProgram.jl:329 solves with
+ * [dl_dz; 0; 0]; moi_wrapper.jl:532-533 forwards the attribute, diff_opt.jl:
+ * 396-402 stores it, the NLP back-end reads it): this is the engine's extension
+ * of it, with the same getters as the reference.
+ * dl_dz n×B×k, dl_dlam m×B×k, dl_dnu p×B×k, seed-major as every _k call; each
+ * may be NULL (= 0) but not all three (−1: there is no unit-seed mode here);
+ * dl_dlam is ignored when m == 0, dl_dnu when p == 0.  out (n+m+p)×B×k =
+ * [dz | dλ | dν].  k ≥ 1, every k through the multi-RHS solve: a seed's block
+ * does not depend on how the seeds are grouped (chunks as the parameter _k
+ * calls, DOPT_QP_JAC_CHUNK included), and with zero dual seeds it is
+ * dopt_qp_reverse_k's (k ≥ 2) bit for bit.  Factorises first if needed; returns
+ * the first singular problem's info.  On the sparse route: k == 1 only (LSQR on
+ * the full LHS), no singular verdict.
+ * dopt_qp_params_reverse_duals_k: the same solve, then the accumulation of
+ * dopt_qp_params_reverse_k (kinds 0-5; out_rev may be NULL); dense-route
+ * handles only. */
+int dopt_qp_reverse_duals_k(dopt_handle* h, int32_t k, const double* dl_dz, const double* dl_dlam,
+                            const double* dl_dnu, double* out);
+int dopt_qp_params_reverse_duals_k(dopt_handle* h, int32_t k, const double* dl_dz, const double* dl_dlam,
+                                   const double* dl_dnu, int32_t nparam, int64_t nterms, const int32_t* t_param,
+                                   const int32_t* t_kind, const int32_t* t_index, const int32_t* t_var,
+                                   const double* t_coef, double* out_rev, double* out_dp);
 
 /* ---- ConicProgram ----------------------------------------------------------
  * A: m×n MOI coefficients (A_moi x + b ∈ K; the diffcp sign flip of
