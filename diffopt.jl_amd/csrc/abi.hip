@@ -291,8 +291,9 @@ int dopt_set_memory(dopt_handle* h, int32_t mem) {
 int dopt_set_sparse(dopt_handle* h, int32_t on) {
   return guarded(h, [&]() {
     if (h->kind != DOPT_KIND_QP && h->kind != DOPT_KIND_CONIC) throw Error(-1, "dopt_set_sparse: QP and conic handles only");
-    if (h->kind == DOPT_KIND_CONIC) {   // A_moi kept sparse by dopt_conic_set_csc (the persistent LSQR on it)
-      h->sparse = on != 0;
+    if (h->kind == DOPT_KIND_CONIC) {   // A_moi kept sparse by dopt_conic_set_csc: the persistent LSQR on it,
+      h->sparse = on != 0;              // or (DOPT_SPARSE_SPLIT) the split LSQR
+      h->sparse_split = on == DOPT_SPARSE_SPLIT;
       h->cset = h->cfactored = false;
       return 0;
     }
@@ -1606,7 +1607,8 @@ int dopt_conic_set_csc(dopt_handle* h, const int64_t* A_colptr, const int64_t* A
     const double* nz = stage_in(*h, h->csc_in_val[0], A_nzval, (size_t)A_nnz);
     const double* A = nullptr;
     if (h->sparse) {   // A_moi kept sparse: CSC + its CSR copy (sparse.hip), no dense A
-      for (int k = 0; k < ncones && cone_desc; ++k)
+      // (the split LSQR applies larger sides from global scratch: dopt_create's cap of 4096 holds)
+      for (int k = 0; k < ncones && cone_desc && !h->sparse_split; ++k)
         if (cone_desc[2 * k] == DOPT_CONE_PSD_TRI && cone_desc[2 * k + 1] > dopt::psd_tri_dim(64))
           throw Error(-1, "sparse conic route: PSD cones up to side 64 (their Dπ apply runs in LDS)");
       if (m) dopt::sp_stage(*h, h->sp[0], cp, rv ? rv : cp, nz, A_nnz, (int)m, h->csc_err.as<int>());

@@ -1611,6 +1611,97 @@ __global__ __launch_bounds__(64 * NW) void conic_split_pass_kernel(
   }
 }
 
+// The pass on a sparse A_moi (dopt_set_sparse(h, DOPT_SPARSE_SPLIT)): the same
+// pair of products from the CSC / CSR arrays of the sparse route.  An output
+// o is row o of A_moi for o < m (CSR row, times x) and column o − m otherwise
+// (CSC column, times w); grid (blocks of SPS_T / G outputs, problems).  One
+// G-lane group per output sums it as SparseA<G>::pair does — lane `sub` the
+// fma chain over entries first + sub, + G, …, then the __shfl_xor tree — so
+// every product entry has the persistent sparse kernel's bits; no atomics.
+// The chain's loads go out SPS_U entries at a time (values and indices, then
+// the gathers) before its fmas consume them in order.  Row outputs take the
+// dense pass's epilogue in the summing lane; column outputs are the whole
+// g[j], written as the only row block's partial (ws.RB = 1), so gpart_sum
+// returns g[j] + 0.  NQ live sequences share each entry's value and index.
+#ifndef DOPT_SPS_T
+#define DOPT_SPS_T 256
+#endif
+#ifndef DOPT_SPS_U
+#define DOPT_SPS_U 4
+#endif
+constexpr int SPS_T = DOPT_SPS_T;   // threads per workgroup (a multiple of 64)
+constexpr int SPS_U = DOPT_SPS_U;   // entries in flight per lane
+
+template <int G, int NQ>
+__device__ __forceinline__ void sp_split_outputs(int dir, const SpConic& sa, const double* __restrict__ bvec,
+                                                 const SplitWS& ws, const int* sq) {
+  const int b = blockIdx.y, m = ws.m, n = ws.n, N = ws.N;
+  const int t = threadIdx.x, sub = t % G;
+  const int o = blockIdx.x * (SPS_T / G) + t / G;
+  const bool live = o < m + n, row = o < m;
+  const double* src[NQ];
+  const double* vecq[NQ];   // what the output's entries multiply: x for a row, w for a column
+  for (int c = 0; c < NQ; ++c) {
+    src[c] = dir == 0 ? ws.vec(ws.v, sq[c]) : ws.vec(ws.u, sq[c]);
+    vecq[c] = row ? src[c] : dir == 0 ? ws.mvec(ws.Dv, sq[c]) : src[c] + n;
+  }
+  const int64_t* ptr = row ? sa.rp + (size_t)b * (m + 1) + o : sa.cp + (size_t)b * (n + 1) + (o - m);
+  const int64_t k0 = live ? ptr[0] : 0, k1 = live ? ptr[1] : 0;
+  const int32_t* __restrict__ idx = row ? sa.ci : sa.ri;
+  const double* __restrict__ val = row ? sa.rv : sa.cv;
+  double acc[NQ];
+  for (int c = 0; c < NQ; ++c) acc[c] = 0.0;
+  for (int64_t k = k0 + sub; k < k1; k += (int64_t)SPS_U * G) {
+    double a[SPS_U], xv[NQ][SPS_U];
+    int32_t id[SPS_U];
+#pragma unroll
+    for (int e = 0; e < SPS_U; ++e) {   // past the end: the last entry again, loaded and not used (no branch per load)
+      const int64_t kk = min(k + (int64_t)e * G, k1 - 1);
+      a[e] = val[kk];
+      id[e] = idx[kk];
+    }
+#pragma unroll
+    for (int e = 0; e < SPS_U; ++e)
+#pragma unroll
+      for (int c = 0; c < NQ; ++c) xv[c][e] = vecq[c][id[e]];
+#pragma unroll
+    for (int e = 0; e < SPS_U; ++e)
+      if (k + (int64_t)e * G < k1) {
+#pragma unroll
+        for (int c = 0; c < NQ; ++c) acc[c] = fma(a[e], xv[c][e], acc[c]);
+      }
+  }
+#pragma unroll
+  for (int c = 0; c < NQ; ++c)
+#pragma unroll
+    for (int s2 = G / 2; s2 > 0; s2 >>= 1) acc[c] += __shfl_xor(acc[c], s2);
+  if (!live || sub != 0) return;
+  for (int c = 0; c < NQ; ++c) {
+    const int bv = sq[c];
+    if (!row) {
+      ws.gpart[(size_t)bv * n + (o - m)] = acc[c];
+      continue;
+    }
+    const double bl = bvec[(size_t)b * m + o], last = src[c][N - 1], sm = src[c][n + o];
+    if (dir == 0) ws.vec(ws.out, bv)[n + o] = fma(bl, last, acc[c] + sm - ws.mvec(ws.Dv, bv)[o]);
+    else ws.mvec(ws.tmpm, bv)[o] = -fma(bl, last, acc[c] + sm);
+  }
+}
+
+template <int G>
+__global__ __launch_bounds__(SPS_T) void conic_sp_split_pass_kernel(
+    int dir, SpConic sa, const double* __restrict__ bvec, SplitWS ws, const LsqrState* __restrict__ stv, int nq) {
+  const int b = blockIdx.y;
+  int sq[2], cnt = 0;
+  for (int q = 0; q < nq; ++q) {
+    const LsqrState& st = stv[q * ws.B + b];
+    if (!(st.done || (dir == 1 && st.skipT))) sq[cnt++] = q * ws.B + b;
+  }
+  if (cnt == 0) return;   // workgroup-uniform
+  if (cnt == 2) sp_split_outputs<G, 2>(dir, sa, bvec, ws, sq);
+  else sp_split_outputs<G, 1>(dir, sa, bvec, ws, sq);
+}
+
 // Dπ (dir 0: Dv = Dπ v_m) or Dπᵀ (dir 1: out_m = Dπᵀ tmpm), one cone per WG
 __global__ __launch_bounds__(CTPB) void conic_split_dpi_kernel(
     int dir, const ConeDesc* __restrict__ cones_g, const double* __restrict__ vcone,
@@ -2463,6 +2554,13 @@ static bool seq_has_output(const ConicSeq& q) {
   return q.dir == CONIC_FWD ? q.out_dx != nullptr : q.out_dA || q.out_db || q.out_dc;
 }
 
+// the sparse route's A_moi (sparse.hip's staging of dopt_conic_set_csc)
+static SpConic sp_conic(const Handle& h) {
+  const SpStore& st = h.sp[0];
+  return SpConic{st.cp.as<int64_t>(), st.rp.as<int64_t>(), st.ri.as<int32_t>(), st.ci.as<int32_t>(), st.cv,
+                 st.rv.as<double>()};
+}
+
 // Split-path LSQR (see conic_split_* above) of the nq (1 or 2) sequences of
 // `seq` per problem (their nq·B right-hand sides from seq[0].rhs on, sequence
 // q·B + b), co-iterated for nq = 2.
@@ -2475,17 +2573,22 @@ static bool seq_has_output(const ConicSeq& q) {
 // instead of leaving it idle between them.  Every sequence's arithmetic is
 // unchanged (a half is the same kernels over fewer problems), so the results
 // are bit-identical to one slice.
-static void conic_lsqr_split(Handle& h, const ConicSeq* seq, int nq) {
+//
+// `sp` (a sparse-split handle): the passes read the sparse route's CSC / CSR
+// arrays (conic_sp_split_pass_kernel) — the six-launch form in one slice, the
+// whole g[j] as the only row block's partial (RB = 1); h.cA is not staged on
+// such a handle and nothing below touches it.
+static void conic_lsqr_split(Handle& h, const ConicSeq* seq, int nq, bool sp) {
   const ConicSeq& q0 = seq[0];
   const ConicSeq q1 = nq > 1 ? seq[1] : ConicSeq{};   // (one sequence: no second set of outputs)
   const int B = (int)h.batch, m = h.m, n = h.n;
   const int maxit = lsqr_maxiter(h);
   const int nc = (int)h.cones.size() / 2;
   const int N = n + m + 1;
-  const int RB = std::max(1, (m + SPLIT_ROWS - 1) / SPLIT_ROWS);
+  const int RB = sp ? 1 : std::max(1, (m + SPLIT_ROWS - 1) / SPLIT_ROWS);
   const size_t M1 = (size_t)std::max(m, 1);
   // fused form: u_n of two sequences in the pass kernel's LDS, v'_n in dpiV's
-  const bool fuse = h.split_fuse && nc > 0 && n <= SPLIT_FUSE_NMAX;
+  const bool fuse = !sp && h.split_fuse && nc > 0 && n <= SPLIT_FUSE_NMAX;
   const int ns = fuse && B >= 2 ? 2 : 1;   // batch slices
   const int PL = 3 * RB + 3 * nc + 4 * CTPB;
   const int Bs0 = (B + ns - 1) / ns;
@@ -2576,16 +2679,27 @@ static void conic_lsqr_split(Handle& h, const ConicSeq* seq, int nq) {
     ws.n = n;
     ws.RB = RB;
     ws.B = S.Bs;
-    S.A = h.cA + (size_t)S.b0 * m * n;
+    S.A = sp ? nullptr : h.cA + (size_t)S.b0 * m * n;
     S.bv = h.cb + (size_t)S.b0 * m;
     S.cv = h.cc + (size_t)S.b0 * n;
     S.vcone = h.vp.as<double>() + (size_t)S.b0 * m;
     S.P = h.dpi.as<double>() + (size_t)S.b0 * h.dpi_len;
     S.gws = h.psd_app.as<double>() + (size_t)nq * S.b0 * h.psd_big_len;
   }
+  const int G = sp ? sp_lanes(2.0 * (double)h.sp[0].nnz / std::max<double>(1.0, (double)B * (m + n))) : 0;
   auto pass = [&](Slice& S, int dir) {
-    hipLaunchKernelGGL(conic_split_pass_kernel<4>, dim3(RB, S.Bs), dim3(256), 0, S.st, dir, S.A, S.bv, S.ws, S.stv,
-                       nq);
+    if (!sp) {
+      hipLaunchKernelGGL(conic_split_pass_kernel<4>, dim3(RB, S.Bs), dim3(256), 0, S.st, dir, S.A, S.bv, S.ws, S.stv,
+                         nq);
+      return;
+    }
+    auto go = [&](auto kern) {   // (one slice: S.b0 = 0, the batch's own arrays)
+      hipLaunchKernelGGL(kern, dim3(std::max(1, (m + n + SPS_T / G - 1) / (SPS_T / G)), S.Bs), dim3(SPS_T), 0, S.st,
+                         dir, sp_conic(h), S.bv, S.ws, S.stv, nq);
+    };
+    if (G == 1) go(conic_sp_split_pass_kernel<1>);
+    else if (G == 4) go(conic_sp_split_pass_kernel<4>);
+    else go(conic_sp_split_pass_kernel<16>);
   };
   auto passT = [&](Slice& S) {
     pass(S, 1);
@@ -2692,13 +2806,6 @@ static bool use_split(const Handle& h) {
   return h.m > 2 * PAIR_ROWS;   // several row blocks per problem: spread them over CUs
 }
 
-// the sparse route's A_moi (sparse.hip's staging of dopt_conic_set_csc)
-static SpConic sp_conic(const Handle& h) {
-  const SpStore& st = h.sp[0];
-  return SpConic{st.cp.as<int64_t>(), st.rp.as<int64_t>(), st.ri.as<int32_t>(), st.ci.as<int32_t>(), st.cv,
-                 st.rv.as<double>()};
-}
-
 // The nq (1 or 2) sequences of `seq` per problem as persistent LSQR runs on
 // the sparse A_moi, side by side in one launch.
 static void conic_lsqr_sparse(Handle& h, const ConicSeq* seq, int nq) {
@@ -2780,6 +2887,7 @@ static void copy_seed_info(Handle& h, int32_t* dst, const int32_t* src) {
 // of one direction (slots SLOT_SEED0 + j, vectors seed-major: seed j's are the
 // batch block at j·B·len).  Routes:
 //   sparse handle        conic_lsqr_kernel<true, G>, one or two sequences per launch
+//   sparse-split handle  conic_lsqr_split on the sparse passes, one or two sequences
 //   use_split            conic_lsqr_split, one or two sequences
 //   one dense sequence   conic_lsqr_kernel<false>
 //   forward + reverse    conic_lsqr2_kernel
@@ -2839,8 +2947,8 @@ static void conic_run(Handle& h, ConicSeq* seq, int nseq) {
     }
     check_launch();
   }
-  if (h.sparse) conic_lsqr_sparse(h, seq, nseq);
-  else if (use_split(h)) conic_lsqr_split(h, seq, nseq);
+  if (h.sparse && !h.sparse_split) conic_lsqr_sparse(h, seq, nseq);
+  else if (h.sparse_split || use_split(h)) conic_lsqr_split(h, seq, nseq, h.sparse_split);
   else if (nseq == 1) conic_lsqr_one(h, seq[0]);
   else if (seeds) conic_lsqr_seeds(h, seq, nseq);
   else conic_lsqr_pair(h, seq[0], seq[1]);

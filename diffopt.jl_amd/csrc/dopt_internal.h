@@ -285,6 +285,7 @@ struct Handle {
   bool small_ready = false;        // the small path's factors are in K (qp_small.hip; dopt_qp_forward reuses them)
   // sparse route (sparse.hip): n + m + p above the dense cap, or dopt_set_sparse
   bool sparse = false;
+  bool sparse_split = false;       // conic, with `sparse`: the split LSQR on the sparse passes (DOPT_SPARSE_SPLIT)
   bool sp_qnz = false;             // some problem's Q has a non-zero value (needs an LU this route lacks)
   SpStore sp[2];                   // G, A
   // the `_csc` calls' tangents (dQ, dG, dA; the conic dA: slot 0), staged like the model's matrices but per

@@ -25,6 +25,7 @@ DOPT_KIND_CONIC = 1
 DOPT_KIND_NLP = 2
 DOPT_MEM_HOST = 0
 DOPT_MEM_DEVICE = 1
+DOPT_SPARSE_SPLIT = 2   # dopt_set_sparse on a conic handle: the split LSQR on the sparse A_moi
 
 CONE_ZEROS, CONE_NONNEG, CONE_NONPOS, CONE_SOC, CONE_PSD_TRI = 0, 1, 2, 3, 4
 

@@ -40,10 +40,23 @@ class ConicBatch:
         self.h = h
         self._mem = None
         self._keep = None
-        # the sparse route (dopt_set_sparse): set_csc keeps A_moi sparse, LSQR matrix-free on it
-        self.sparse = bool(sparse)
-        if sparse:
-            _lib.check(self.lib.dopt_set_sparse(self.h, 1), self.h)
+        # the sparse route (dopt_set_sparse): set_csc keeps A_moi sparse, LSQR matrix-free on it.
+        # sparse=True: one workgroup per problem, PSD sides up to 64; sparse="split": the split
+        # LSQR on the sparse A_moi (DOPT_SPARSE_SPLIT), PSD sides up to 4096
+        self.sparse = False
+        self.sparse_split = False
+        if isinstance(sparse, str) or sparse:
+            self.set_sparse(sparse)
+
+    def set_sparse(self, sparse):
+        """Switch the handle's route (``False``, ``True`` or ``"split"``); the model is
+        dropped and has to be set again."""
+        if isinstance(sparse, str) and sparse != "split":
+            raise ValueError(f'sparse={sparse!r}: expected False, True or "split"')
+        mode = _lib.DOPT_SPARSE_SPLIT if sparse == "split" else 1 if sparse else 0
+        _lib.check(self.lib.dopt_set_sparse(self.h, mode), self.h)
+        self.sparse = mode != 0
+        self.sparse_split = mode == _lib.DOPT_SPARSE_SPLIT
 
     def close(self):
         if getattr(self, "h", None):

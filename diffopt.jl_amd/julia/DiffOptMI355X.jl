@@ -18,7 +18,9 @@
 # sensitivity surface).  Not exercised in CI: the build image has no Julia
 # (SURVEY.md §8(c)); the C-ABI it binds is exercised by the Python ctypes
 # harness.  That holds for the `dual_seeds` path of QPModel too: its
-# dopt_qp_reverse_duals_k call is tested through ctypes only.
+# dopt_qp_reverse_duals_k call is tested through ctypes only, and for
+# ConicModel's `sparse` keyword (`:split` → dopt_set_sparse(h, 2)): NOT
+# EXECUTED here; tests/test_sparse_split_gpu.py runs that mode through ctypes.
 module DiffOptMI355X
 
 import DiffOpt
@@ -374,12 +376,23 @@ mutable struct ConicModel <: DiffOpt.AbstractModel
     handle::Union{Nothing,Handle}
     staged::Any                          # (A, b, c, x, s, y, cones) the handle holds, or nothing
     device::Int
+    sparse::Union{Bool,Symbol}           # :auto (by size, density and PSD sides), false, true, or :split
 end
 
-function ConicModel(; device::Integer = 0)
+# `sparse`: how A_moi is held on the device.  :auto — sparse (dopt_set_sparse(h, 1))
+# for a large, sparse A_moi whose PSD sides are at most 64, dense otherwise; false /
+# true — always dense / always mode 1 (which refuses PSD sides above 64); :split —
+# dopt_set_sparse(h, DOPT_SPARSE_SPLIT): sparse A_moi under the split LSQR, PSD
+# sides up to 4096 (as ConicBatch(sparse = "split") of the Python package).
+function ConicModel(; device::Integer = 0, sparse::Union{Bool,Symbol} = :auto)
+    sparse isa Symbol && !(sparse in (:auto, :split)) &&
+        error("diffopt_mi355x: ConicModel(sparse = $sparse): expected :auto, false, true or :split")
     inner = CP.Model()
-    return ConicModel(inner, inner.model, inner.input_cache, inner.x, inner.s, inner.y, nothing, nothing, device)
+    return ConicModel(inner, inner.model, inner.input_cache, inner.x, inner.s, inner.y, nothing, nothing, device,
+                      sparse)
 end
+
+const SPARSE_SPLIT = Int32(2)   # DOPT_SPARSE_SPLIT (include/diffopt_mi355x.h)
 
 MOI.is_empty(m::ConicModel) = MOI.is_empty(m.inner)
 function MOI.empty!(m::ConicModel)
@@ -447,8 +460,16 @@ function _ensure!(m::ConicModel)
         # a large, sparse A_moi stays sparse on the device (dopt_set_sparse: LSQR
         # on the matrix-free M from its CSC / CSR, as the reference's own lsqr on
         # a SparseMatrixCSC, ConicProgram.jl:323, :372) instead of an m×n dense copy
-        if mr * n > 4_000_000 && SparseArrays.nnz(Amoi) < 0.05 * mr * n && _sparse_cones_ok(desc)
-            _check(ccall((:dopt_set_sparse, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, Int32(1)), h.ptr)
+        mode = if m.sparse === :split
+            SPARSE_SPLIT
+        elseif m.sparse === true || (m.sparse === :auto && mr * n > 4_000_000 &&
+                                     SparseArrays.nnz(Amoi) < 0.05 * mr * n && _sparse_cones_ok(desc))
+            Int32(1)
+        else
+            Int32(0)
+        end
+        if mode != 0
+            _check(ccall((:dopt_set_sparse, LIB), Cint, (Ptr{Cvoid}, Int32), h.ptr, mode), h.ptr)
             h.sparse = true
         end
     end
@@ -468,7 +489,7 @@ function _ensure!(m::ConicModel)
     return h
 end
 
-# the sparse conic route takes PSD cones up to side 64 (include/diffopt_mi355x.h)
+# the one-workgroup sparse conic route (mode 1) takes PSD cones up to side 64 (include/diffopt_mi355x.h)
 _sparse_cones_ok(desc) = all(k -> desc[2k-1] != 4 || desc[2k] <= 64 * 65 ÷ 2, 1:(length(desc) ÷ 2))
 
 # forward_differentiate! (ConicProgram.jl:257-334): the tangents gathered with

@@ -94,10 +94,19 @@ int dopt_set_memory(dopt_handle* h, int32_t mem);
 int dopt_qp_set(dopt_handle* h, const double* Q, const double* G,
                 const double* hvec, const double* A, const double* z,
                 const double* lam, const double* nu);
-/* Sparse route (sparse.hip; on = 1).  CONIC handles: dopt_conic_set_csc keeps
+/* Sparse route (sparse.hip; on = 1, or 2 on a conic handle).  CONIC handles: dopt_conic_set_csc keeps
  * A_moi as CSC plus a CSR copy (no dense m×n A) and every LSQR run applies M
  * matrix-free from them (ConicProgram.jl:243-247, :323, :372), one workgroup per
- * problem; PSD cones up to side 64; dopt_conic_set (dense) is refused.  The
+ * problem; PSD cones up to side 64; dopt_conic_set (dense) is refused.
+ * on = DOPT_SPARSE_SPLIT (2), conic handles only: the same sparse A_moi under
+ * the split LSQR — every iteration's products spread over the device (one
+ * lane group per row / column of A_moi, grid of output blocks × problems), Dπ
+ * one workgroup per cone, and PSD cones of any side up to dopt_create's 4096
+ * (sides above 64 apply Dπ from global scratch).  The products are summed as
+ * on = 1 sums them; LSQR's vector sums are the split path's, so the two modes
+ * agree to LSQR's stopping noise, not bit for bit.  on = 1 stays the default
+ * sparse mode; nothing picks the mode from the cone list.  Any other non-zero
+ * `on` means 1.  The
  * matrix tangent and the matrix gradient have sparse forms on every conic
  * route (dopt_conic_forward_csc, dopt_conic_reverse_grads_csc below); the dense
  * dA / out_dA arguments of the other calls remain optional (NULL = skip).
@@ -118,6 +127,7 @@ int dopt_qp_set(dopt_handle* h, const double* Q, const double* G,
  * dopt_qp_reverse_grads_csc (sparse tangents with their own patterns, gradients
  * sampled on a pattern); dopt_qp_forward's dense dQ / dG / dA still work here
  * (NULL = zero) for problems small enough to hold them. */
+#define DOPT_SPARSE_SPLIT 2
 int dopt_set_sparse(dopt_handle* h, int32_t on);
 /* LSQR statistics of the sparse route's last solves, 4·B int32: per problem
  * [istop | iterations] of the reverse run, then of the forward run. */
